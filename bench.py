@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark: device-resident batched parse of packet slabs on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`,
+`GB/s`); --dump-outputs DIR also writes the last timed step's columns as DIR/<column>.npy.  Everything
+else below (device-event timing, roofline, ceiling probes, batched launches, "c5", "c3", "c4", "host",
+"pcap", "host_pcap", "pcap_stream", "cpu_baseline") is measured only with --full.
 
 A step = one parse of one batch of 2^20 packets per GPU (config C2 by default: 64-byte
 Ether/IPv4/UDP, fixed stride) producing the chain + Ether/IPv4/UDP field tuple + recomputed IPv4
@@ -18,7 +23,7 @@ torch.distributed.run rank 0 is that process and the other ranks wait at a CPU (
 without touching a GPU.  The "c5" record times the C5 config through pkt_mgpu_parse_gather: 2^24
 packets in contiguous shards, parse and RCCL gather of the used tuple bytes to device 0 timed
 separately.
-At N = 1 the line also carries the other device-resident BASELINE configs ("c3", "c4": each with its own
+At N = 1 the --full line also carries the other device-resident BASELINE configs ("c3", "c4": each with its own
 roofline), the host-memory rate ("host": pinned zero-copy pkt_parse_host), the capture path ("pcap":
 capture in HBM -> pkt_pcap_index_device -> parse, one step; "pcap.index": the index kernels alone) and
 the capture in host memory ("host_pcap").
@@ -70,6 +75,13 @@ def parse_args():
                     help="TEST MODE: --gpus N shards on device 0 (pkt_mgpu_create_virtual, device copies instead "
                          "of RCCL) to run the N-device code paths on one GPU; prints a line labelled as a smoke, "
                          "never a measurement or a scaling point")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: device-event timing, roofline and ceiling "
+                         "probes, batched launches, C5, the C3/C4/host/pcap records and the CPU baseline "
+                         "(each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the columns of the last timed step's output set as "
+                         "DIR/<column>.npy (float32 / float64; a fixed seeded sample of the packets above 64 MB)")
     return ap.parse_args()
 
 
@@ -183,6 +195,43 @@ def packed_outputs(torch, dev, cols, n, count):
         buf = torch.empty(max(1, nb), dtype=torch.uint8, device=dev)
         outs.append((buf, mgpu.packed_views(buf, cols, n)))
     return outs
+
+
+DUMP_BUDGET = 60 << 20  # array bytes per --dump-outputs run (with the .npy headers: under 64 MB)
+
+
+def dump_outputs(path, views_per_dev, n):
+    """--dump-outputs: the columns a caller of the timed path receives from its last timed step, one
+    DIR/<column>.npy per column (device i > 0: <column>.dev<i>.npy).  Integer columns of up to 16 bits
+    are written as float32 and wider ones as float64, both exact (the widest values are 48-bit MAC
+    addresses).  Slot rows at or past a packet's n_hdrs are unspecified (never read by a caller) and are
+    written as 0.  Above the budget every column holds the same seeded sample of the packets, whose
+    indices go to sample_index.npy."""
+    from pktgpu import schema
+    os.makedirs(path, exist_ok=True)
+
+    def width(c):
+        return 4 if schema.column_dtype(c).itemsize <= 2 else 8
+    cols = list(views_per_dev[0])
+    slots = {c for c, _, shp, _ in schema.OUT_COLUMNS if shp == "slots"}
+    per_pkt = sum(int(np.prod(schema.column_shape(c, 1))) * width(c) for c in cols) * len(views_per_dev)
+    m = min(n, DUMP_BUDGET // (per_pkt + 8))
+    idx = None
+    if m < n:
+        idx = np.sort(np.random.default_rng(0x5EED0D0D).choice(n, m, replace=False))
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    for i, views in enumerate(views_per_dev):
+        host = {c: v.cpu().numpy() for c, v in views.items()}
+        for c, a in host.items():
+            if c in slots:  # slot-major [MAX_HDRS][n]
+                if "n_hdrs" not in host:
+                    continue
+                a = np.where(np.arange(schema.MAX_HDRS)[:, None] < host["n_hdrs"][None, :], a, 0)
+                a = a[:, idx] if idx is not None else a
+            elif idx is not None:
+                a = a[idx]
+            name = c if i == 0 else f"{c}.dev{i}"
+            np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if width(c) == 4 else np.float64))
 
 
 def load_probe():
@@ -676,50 +725,55 @@ def run_mgpu(args, ndev):
     timed()
     MP.synchronize()
     elapsed = time.perf_counter() - t0
-    # the same K steps again with one event pair on device 0's work stream (the extra streams start
-    # after it and are joined back into it): device 0's time per step, outside the timed region
-    ext0 = MP.streams()[0]
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(ext0)
-    timed()
-    e1.record(ext0)
-    MP.synchronize()
-    region_ms = e0.elapsed_time(e1)
-
-    # ---------------- roofline sub-phase on device 0 (its own ctx, same buffers)
-    P = pktgpu.Parser(0)
-    P.set_fastpath(args.fastpath)
-    P.set_staging(args.staging)
-    P.set_window(args.window)
+    if args.dump_outputs and args.steps > 0:
+        last = (total_steps - 1) % ring  # the output set of the last timed step
+        dump_outputs(args.dump_outputs, [pd["outs"][last][1] for pd in per], n)
     p0 = per[0]
-    batches0 = [P._batch(p0["slabs"][r], n, p0["stride"], p0["offs"], p0["lens"]) for r in range(ring)]
-    ostructs0 = [P.out_struct(p0["outs"][r][1]) for r in range(ring)]
     o0 = p0["outs"][0][1]
     used_slots = int(o0["n_hdrs"].max().item()) if "n_hdrs" in o0 else 0
-    R = min(max(args.steps, 20), 50)
-    default_shape = args.columns == default_cols
-    copy_args = None
-    if args.config == "c2" and default_shape:  # the streaming-copy ceiling of the C2 bytes
-        copy_args = ([p0["outs"][r][0] for r in range(ring)], p0["slab_np"].size,
-                     schema.bytes_per_packet(cols, n_slots=max(used_slots, 1)) * n)
-    kern, ceil_, copy_, scopy = roofline_phase(torch, P, args.config, args.config in ("c2", "c3", "c5") and default_shape,
-                                               batches0, ostructs0, p0["slabs"], ring, n, p0["stride"], entry,
-                                               MP.torch_devices[0], used_slots, R, copy_args)
+    if args.full:
+        # the same K steps again with one event pair on device 0's work stream (the extra streams start
+        # after it and are joined back into it): device 0's time per step, outside the timed region
+        ext0 = MP.streams()[0]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(ext0)
+        timed()
+        e1.record(ext0)
+        MP.synchronize()
+        region_ms = e0.elapsed_time(e1)
 
-    # ---------------- multi-batch launch (pkt_parse_batches): K ring batches in ONE launch, so the
-    # launch's ramp and drain are paid once per K batches (same bytes per batch as `roofline`)
-    batched = None
-    kb = min(16, ring)
-    if kb >= 2:
-        rs = torch.cuda.Stream(MP.torch_devices[0])
-        call = P.batches_call(batches0[:kb], ostructs0[:kb], entry, rs)
-        bt = [event_avg_ms(torch, rs, lambda k, s: call(), max(4, min(R, 20))) for _ in range(5)]
-        batched = {"entry": "pkt_parse_batches", "batches_per_launch": kb, "packets_per_batch": n,
-                   "avg_launch_us": round(float(np.median(bt)) * 1e3, 3),
-                   "us_per_batch": round(float(np.median(bt)) * 1e3 / kb, 3)}
+        # ---------------- roofline sub-phase on device 0 (its own ctx, same buffers)
+        P = pktgpu.Parser(0)
+        P.set_fastpath(args.fastpath)
+        P.set_staging(args.staging)
+        P.set_window(args.window)
+        batches0 = [P._batch(p0["slabs"][r], n, p0["stride"], p0["offs"], p0["lens"]) for r in range(ring)]
+        ostructs0 = [P.out_struct(p0["outs"][r][1]) for r in range(ring)]
+        R = min(max(args.steps, 20), 50)
+        default_shape = args.columns == default_cols
+        copy_args = None
+        if args.config == "c2" and default_shape:  # the streaming-copy ceiling of the C2 bytes
+            copy_args = ([p0["outs"][r][0] for r in range(ring)], p0["slab_np"].size,
+                         schema.bytes_per_packet(cols, n_slots=max(used_slots, 1)) * n)
+        kern, ceil_, copy_, scopy = roofline_phase(torch, P, args.config,
+                                                   args.config in ("c2", "c3", "c5") and default_shape,
+                                                   batches0, ostructs0, p0["slabs"], ring, n, p0["stride"], entry,
+                                                   MP.torch_devices[0], used_slots, R, copy_args)
+
+        # ---------------- multi-batch launch (pkt_parse_batches): K ring batches in ONE launch, so the
+        # launch's ramp and drain are paid once per K batches (same bytes per batch as `roofline`)
+        batched = None
+        kb = min(16, ring)
+        if kb >= 2:
+            rs = torch.cuda.Stream(MP.torch_devices[0])
+            call = P.batches_call(batches0[:kb], ostructs0[:kb], entry, rs)
+            bt = [event_avg_ms(torch, rs, lambda k, s: call(), max(4, min(R, 20))) for _ in range(5)]
+            batched = {"entry": "pkt_parse_batches", "batches_per_launch": kb, "packets_per_batch": n,
+                       "avg_launch_us": round(float(np.median(bt)) * 1e3, 3),
+                       "us_per_batch": round(float(np.median(bt)) * 1e3 / kb, 3)}
 
     c5 = None
-    if args.config == "c2" and not args.no_c5:
+    if args.full and args.config == "c2" and not args.no_c5:
         # (after the headline's timed region: a failure here, e.g. RCCL on a new node, is recorded in
         # the line instead of losing it)
         try:
@@ -737,7 +791,6 @@ def run_mgpu(args, ndev):
     algo = read_b + write_b
     slab_bytes = p0["slab_np"].size
     value = ndev * n * args.steps / elapsed / 1e9
-    pipe_s = region_ms * 1e-3 / args.steps
     agg_gbs = algo * ndev * args.steps / elapsed / 1e9
     res = {
         "metric": METRIC,
@@ -765,19 +818,21 @@ def run_mgpu(args, ndev):
                  "algorithmic_bytes_per_pkt": {"read": read_b / n, "written": write_b / n},
                  "aggregate_frac_of_n_x_peak": round(agg_gbs / (ndev * HBM_PEAK_GBS), 4)},
     }
-    assemble(args, res, n, ndev, cols, read_b, write_b, kern, ceil_, copy_, R, slab_bytes, p0["stride"],
-             p0["offs_np"], span, pipe_s, scopy)
-    if batched is not None:
-        bs = batched["us_per_batch"] * 1e-6
-        batched.update({"achieved": round(algo / bs / 1e9, 2), "frac": round(algo / bs / 1e9 / HBM_PEAK_GBS, 4),
-                        "frac_kind": "algorithmic bytes of one batch / (one K-batch launch's duration / K), "
-                                     "HIP events on one stream, median of 5 rounds / 8 TB/s; the headline "
-                                     "`value` stays one launch per 2^20-packet batch"})
-        res["roofline"]["batched"] = batched
-    res["timing"] = {"wall_ms": round(elapsed * 1e3, 4), "device0_ms_same_steps_repeated": round(region_ms, 4),
-                     "wall_minus_device_ms": round(elapsed * 1e3 - region_ms, 4),
-                     "what": "wall = the timed region (one foreign call issuing K steps + synchronize); "
-                             "device = the same K steps re-issued between one HIP event pair on device 0"}
+    if args.full:
+        pipe_s = region_ms * 1e-3 / args.steps
+        assemble(args, res, n, ndev, cols, read_b, write_b, kern, ceil_, copy_, R, slab_bytes, p0["stride"],
+                 p0["offs_np"], span, pipe_s, scopy)
+        if batched is not None:
+            bs = batched["us_per_batch"] * 1e-6
+            batched.update({"achieved": round(algo / bs / 1e9, 2), "frac": round(algo / bs / 1e9 / HBM_PEAK_GBS, 4),
+                            "frac_kind": "algorithmic bytes of one batch / (one K-batch launch's duration / K), "
+                                         "HIP events on one stream, median of 5 rounds / 8 TB/s; the headline "
+                                         "`value` stays one launch per 2^20-packet batch"})
+            res["roofline"]["batched"] = batched
+        res["timing"] = {"wall_ms": round(elapsed * 1e3, 4), "device0_ms_same_steps_repeated": round(region_ms, 4),
+                         "wall_minus_device_ms": round(elapsed * 1e3 - region_ms, 4),
+                         "what": "wall = the timed region (one foreign call issuing K steps + synchronize); "
+                                 "device = the same K steps re-issued between one HIP event pair on device 0"}
     if c5 is not None:
         res["c5"] = c5
     if args.virtual:
@@ -788,22 +843,23 @@ def run_mgpu(args, ndev):
         res["scaling"] = None
         res["config"]["parallelism"] = f"virtual{ndev} on one GPU"
         res["config"]["launch"] += " (virtual handle: one physical device, gather messages by hipMemcpyAsync)"
-    if ndev == 1 and not args.no_extra and args.config == "c2":
-        # the other single-GPU BASELINE configs, device-resident, each with its own roofline
-        for cfg in ("c3", "c4"):
-            res[cfg] = config_record(args, torch, MP, P, cfg, entry)
-    if ndev == 1 and not args.no_extra:
-        res["host"] = host_record(P, torch, cols)
-        res["pcap"] = pcap_record(P, torch, MP.torch_devices[0])
-        res["host_pcap"] = host_pcap_record(P)
-        res["pcap_stream"] = pcap_stream_record(P)
-    if ndev == 1 and not args.no_cpu_baseline:
-        cores, aff, quota = host_cores()
-        threads = args.cpu_threads or cores
-        res["cpu_baseline"] = cpu_baseline(p0["slab_np"], p0["stride"], p0["offs_np"], p0["lens_np"], n, cols, threads)
-        res["cpu_baseline"]["host"] = {"affinity_cpus": aff, "cgroup_cpu_quota": quota,
-                                       "os_cpu_count": os.cpu_count()}
-    P.close()
+    if args.full:
+        if ndev == 1 and not args.no_extra and args.config == "c2":
+            # the other single-GPU BASELINE configs, device-resident, each with its own roofline
+            for cfg in ("c3", "c4"):
+                res[cfg] = config_record(args, torch, MP, P, cfg, entry)
+        if ndev == 1 and not args.no_extra:
+            res["host"] = host_record(P, torch, cols)
+            res["pcap"] = pcap_record(P, torch, MP.torch_devices[0])
+            res["host_pcap"] = host_pcap_record(P)
+            res["pcap_stream"] = pcap_stream_record(P)
+        if ndev == 1 and not args.no_cpu_baseline:
+            cores, aff, quota = host_cores()
+            threads = args.cpu_threads or cores
+            res["cpu_baseline"] = cpu_baseline(p0["slab_np"], p0["stride"], p0["offs_np"], p0["lens_np"], n, cols, threads)
+            res["cpu_baseline"]["host"] = {"affinity_cpus": aff, "cgroup_cpu_quota": quota,
+                                           "os_cpu_count": os.cpu_count()}
+        P.close()
     MP.close()
     return res
 

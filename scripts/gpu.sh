@@ -8,7 +8,7 @@
 # steps
 #   tests              pytest -m gpu (the whole parity suite)
 #   smoke              __graft_entry__.smoke()
-#   bench[=ARGS]       python bench.py ARGS (default: the driver's --steps 20 --warmup 5)
+#   bench[=ARGS]       python bench.py ARGS (default: --full --steps 20 --warmup 5, the whole line)
 #   prof[=CFG]         rocprofv3 --kernel-trace --stats of bench.py --config CFG (one stream)
 #   traffic[=CFG]      FETCH_SIZE (x2, gfx950) and WRITE_SIZE passes of the same -> traffic.json
 #   kbench=CFG:VARS:WINDOWS:STAGING   scripts/kbench.py, 1 and 2 streams, 3 rounds
@@ -45,15 +45,15 @@ for step in "$@"; do
   case $key in
     tests) run tests 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider ;;
     smoke) run smoke 300 python -c 'import __graft_entry__ as g; g.smoke()' ;;
-    bench) run bench${arg:+_$(echo $arg | tr -c 'a-z0-9' '_')} 600 python bench.py ${arg:---steps 20 --warmup 5} ;;
+    bench) run bench${arg:+_$(echo $arg | tr -c 'a-z0-9' '_')} 600 python bench.py ${arg:---full --steps 20 --warmup 5} ;;
     prof)  c=${arg:-c2}
            run prof_$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$c" -o trace -- \
-               python bench.py --config $c --steps 50 --warmup 5 --no-cpu-baseline --no-c5 --no-extra --streams 1 ;;
+               python bench.py --config $c --steps 50 --warmup 5 --full --no-cpu-baseline --no-c5 --no-extra --streams 1 ;;
     traffic) c=${arg:-c2}
            run fetch_$c 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_$c" -o pmc -- \
-               python bench.py --config $c --steps 20 --warmup 2 --no-cpu-baseline --no-c5 --no-extra --streams 1
+               python bench.py --config $c --steps 20 --warmup 2 --full --no-cpu-baseline --no-c5 --no-extra --streams 1
            run write_$c 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_$c" -o pmc -- \
-               python bench.py --config $c --steps 20 --warmup 2 --no-cpu-baseline --no-c5 --no-extra --streams 1
+               python bench.py --config $c --steps 20 --warmup 2 --full --no-cpu-baseline --no-c5 --no-extra --streams 1
            run traffic_$c 60 python scripts/traffic.py "$OUT/pmc_fetch_$c" "$OUT/pmc_write_$c" "$OUT/traffic_$c.json" parse_kernel "$TAG $c" ;;
     kbench) IFS=: read -r c v w st <<< "$arg"
            run kbench_${c}_st${st:-0} 300 python scripts/kbench.py --config $c --variants "${v:-status;chain;all}" --windows ${w:-0} \

@@ -40,6 +40,48 @@ def test_line_bytes_indexed_vs_brute_force():
         assert bench.line_bytes(n, None, offs[perm].astype(np.uint64), span[perm]) == brute_lines(offs, span)
 
 
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: one exact float .npy per column, unused slot rows as 0, and above the budget the
+    same seeded sample of packets from every column, identical from run to run."""
+    import pytest
+    torch = pytest.importorskip("torch")
+    from pktgpu import schema
+    n = 1000
+    rng = np.random.default_rng(3)
+    nh = rng.integers(0, 5, n).astype(np.uint8)
+    cols = {"n_hdrs": nh,
+            "hdr_off": rng.integers(0, 1 << 16, (schema.MAX_HDRS, n)).astype(np.uint16),
+            "eth_src": rng.integers(0, 1 << 48, n).astype(np.uint64),
+            "ipv4_src": rng.integers(0, 1 << 32, n).astype(np.uint32),
+            "ipv6_src": rng.integers(0, 256, (n, 16)).astype(np.uint8)}
+    views = {c: torch.from_numpy(a) for c, a in cols.items()}
+    used = np.arange(schema.MAX_HDRS)[:, None] < nh[None, :]
+
+    bench.dump_outputs(str(tmp_path / "all"), [views], n)
+    got = {c: np.load(tmp_path / "all" / f"{c}.npy") for c in cols}
+    assert sorted(p.name for p in (tmp_path / "all").iterdir()) == sorted(f"{c}.npy" for c in cols)
+    assert got["n_hdrs"].dtype == np.float32 and got["hdr_off"].dtype == np.float32
+    assert got["eth_src"].dtype == np.float64 and got["ipv4_src"].dtype == np.float64
+    for c in ("n_hdrs", "eth_src", "ipv4_src", "ipv6_src"):
+        assert np.array_equal(got[c].astype(cols[c].dtype), cols[c]), c
+    assert np.array_equal(got["hdr_off"], np.where(used, cols["hdr_off"], 0))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 20000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), [views], n)
+    idx = np.load(tmp_path / "s1" / "sample_index.npy").astype(np.int64)
+    assert 0 < len(idx) < n and np.all(np.diff(idx) > 0) and idx[-1] < n
+    total = 0
+    for p in sorted((tmp_path / "s1").iterdir()):
+        a = np.load(p)
+        total += a.nbytes
+        assert np.array_equal(a, np.load(tmp_path / "s2" / p.name)), p.name
+    assert total <= 20000
+    assert np.array_equal(np.load(tmp_path / "s1" / "eth_src.npy"), cols["eth_src"][idx].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "s1" / "hdr_off.npy"), np.where(used, cols["hdr_off"], 0)[:, idx])
+    assert np.array_equal(np.load(tmp_path / "s1" / "ipv6_src.npy"), cols["ipv6_src"][idx])
+
+
 def test_gpus_beyond_visible_devices_exits_nonzero():
     """`bench.py --gpus N` with fewer visible devices must fail.  This container has
     no GPU."""

@@ -311,7 +311,7 @@ def test_bench_mgpu_leg_at_one_device():
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "6",
-                        "--warmup", "2", "--no-cpu-baseline", "--no-extra", "--ring-gib", "0.25",
+                        "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extra", "--ring-gib", "0.25",
                         "--total-packets", str(1 << 21)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -202,7 +202,7 @@ def test_bench_virtual_eight_shards_smoke():
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "8", "--virtual", "--steps", "4",
-                        "--warmup", "1", "--no-cpu-baseline", "--ring-gib", "0.0625",
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--ring-gib", "0.0625",
                         "--total-packets", str((1 << 21) + 5)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
