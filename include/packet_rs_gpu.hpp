@@ -207,6 +207,23 @@ class Parser {
         return r;
     }
 
+    // tests/pcap.rs:7-37 (`pcap_write`) on the GPU: the packets of a device batch with select[i] != 0
+    // (select NULL: all), in batch order, as one capture in the device buffer `dst` (16-byte aligned,
+    // dst_len bytes), every record stamped (tv_sec, tv_usec) as the reference stamps one time on the file.
+    // Returns the capture's size; *n_out = its record count.  Throws with the size needed when the
+    // capture is larger than dst_len.
+    uint64_t pcap_write(const pkt_batch_t& b, uint8_t* dst, uint64_t dst_len, const uint8_t* select = nullptr,
+                        uint32_t tv_sec = 0, uint32_t tv_usec = 0, uint64_t* n_out = nullptr, hipStream_t s = nullptr) {
+        uint64_t total = 0, n = 0;
+        const int rc = pkt_pcap_write(ctx_, &b, select, 0, tv_sec, tv_usec, nullptr, nullptr, dst, dst_len, nullptr,
+                                      nullptr, nullptr, &total, &n, s);
+        if (n_out) *n_out = n;
+        if (rc != PKT_SUCCESS && total > dst_len)
+            throw std::length_error("pkt_pcap_write: the capture needs " + std::to_string(total) + " bytes");
+        check(rc, ctx_, "pkt_pcap_write");
+        return total;
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

@@ -499,6 +499,51 @@ int pkt_parse_pcap_async(pkt_ctx_t *ctx, const uint8_t *buf, uint64_t len, int e
                          uint64_t *offsets, uint32_t *lens, uint64_t cap, void *stream);
 int pkt_parse_pcap_result(pkt_ctx_t *ctx, uint64_t *n_out);
 
+/* ---- writing a capture ----
+ * tests/pcap.rs:7-37 as a batch operation: the selected packets of `batch`, in batch order, as one
+ * capture in dst: the 24-byte global header of pcap.rs:20-23, then per packet a 16-byte record header
+ * (tv_sec, tv_usec, incl_len, orig_len, little-endian u32, pcap.rs:27-32) and incl_len packet bytes.
+ *  - batch: any pkt_batch_t, fixed-stride or indexed, under its usual slab rules (the slab is only read,
+ *    so indexed offsets need not be ordered and may overlap).  len_i = the batch's packet length, clamped
+ *    to the slab end and to 65535.
+ *  - select: device [n] or NULL (every packet); packet i is written iff select[i] != 0.
+ *  - snaplen: 0 = no truncation, else incl_len = min(len_i, snaplen); orig_len = len_i always (with
+ *    snaplen 0 the reference's `plen, plen`).  The global header is always the reference's 24 bytes
+ *    (file snaplen 0xffff).
+ *  - ts_sec / ts_usec: device [n] arrays indexed by the SOURCE packet i, each NULL for the constant
+ *    tv_sec / tv_usec (the reference stamps one time on the whole file).
+ *  - dst: device memory, 16-byte aligned, dst_len bytes of capacity.  total = 24 + sum over the selected
+ *    packets of (16 + incl_len), as uint64.  Bytes [0, total) are written, each once and fully defined;
+ *    nothing at or past total is written and no byte of dst is read.  If total > dst_len the call
+ *    returns PKT_ERR_INVALID_ARG with *bytes_out = total and *n_out = the selected count (the capacity
+ *    to retry with); dst's contents are then unspecified, but nothing outside [0, dst_len) is written.
+ *    (The decision is taken on the device, where total is known: the writing kernels read it and exit.)
+ *  - rec_offsets / rec_lens / src_index: device arrays sized for n, each may be NULL.  For the k-th
+ *    written record: its data offset in dst, its incl_len (what pkt_pcap_index returns on the result, so
+ *    {dst, total, rec_offsets, rec_lens, *n_out} is an indexed pkt_batch_t) and its source packet index.
+ *    Entries at index >= *n_out are not written.
+ *  - n may be 0 and the selection may be empty: the 24-byte header alone.  n >= 2^32 is
+ *    PKT_ERR_INVALID_ARG.
+ * pkt_pcap_write is blocking: one host wait, for the two totals (work is ordered on `stream`).
+ * pkt_pcap_write_async queues the same work and returns; the totals go to pinned words of the ctx and
+ * pkt_pcap_write_result waits for them and gives the outcome as pkt_pcap_write's.  One write in flight
+ * per ctx: another write on the ctx before the result is taken fails with PKT_ERR_INVALID_ARG.
+ * pkt_pcap_write_host is the same operation on HOST pointers (batch, select, ts_*, dst and the three
+ * outputs) and needs no device or ctx, like pkt_pcap_index. */
+int pkt_pcap_write(pkt_ctx_t *ctx, const pkt_batch_t *batch, const uint8_t *select, uint32_t snaplen,
+                   uint32_t tv_sec, uint32_t tv_usec, const uint32_t *ts_sec, const uint32_t *ts_usec,
+                   uint8_t *dst, uint64_t dst_len, uint64_t *rec_offsets, uint32_t *rec_lens,
+                   uint32_t *src_index, uint64_t *bytes_out, uint64_t *n_out, void *stream);
+int pkt_pcap_write_async(pkt_ctx_t *ctx, const pkt_batch_t *batch, const uint8_t *select, uint32_t snaplen,
+                         uint32_t tv_sec, uint32_t tv_usec, const uint32_t *ts_sec, const uint32_t *ts_usec,
+                         uint8_t *dst, uint64_t dst_len, uint64_t *rec_offsets, uint32_t *rec_lens,
+                         uint32_t *src_index, void *stream);
+int pkt_pcap_write_result(pkt_ctx_t *ctx, uint64_t *bytes_out, uint64_t *n_out);
+int pkt_pcap_write_host(const pkt_batch_t *batch, const uint8_t *select, uint32_t snaplen, uint32_t tv_sec,
+                        uint32_t tv_usec, const uint32_t *ts_sec, const uint32_t *ts_usec, uint8_t *dst,
+                        uint64_t dst_len, uint64_t *rec_offsets, uint32_t *rec_lens, uint32_t *src_index,
+                        uint64_t *bytes_out, uint64_t *n_out);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -940,6 +940,12 @@ int pkt_ctx_destroy(pkt_ctx_t* ctx) {
         (void)hipFree(ctx->pc.buf);
         (void)hipHostFree(ctx->pc.ctl);
     }
+    if (ctx && (ctx->pw.buf || ctx->pw.ctl)) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(ctx->pw.buf);
+        (void)hipHostFree(ctx->pw.ctl);
+    }
     if (ctx && ctx->hp.init) {
         (void)hipSetDevice(ctx->device);
         for (int k = 0; k < HostPipe::kSlots; k++) {

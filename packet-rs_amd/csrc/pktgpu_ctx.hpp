@@ -55,6 +55,19 @@ struct PcapScratch {
     hipStream_t pending_stream = nullptr;
 };
 
+// Scratch of pkt_pcap_write (pktgpu_pcapw.hip), grown on demand: the totals' device words, the tile
+// sums, the window table and the record-table columns the caller did not ask for.
+struct PcapWriteScratch {
+    void* buf = nullptr;
+    uint64_t bytes = 0;
+    uint64_t* ctl = nullptr;      // pinned host words: [total bytes, records]
+    uint64_t* ctl_dev = nullptr;  // the same words as the device addresses them
+    uint64_t dst_len = 0;         // the last queued write's capacity (total > dst_len = it did not fit)
+    // a write queued by pkt_pcap_write_async whose result has not been taken: one in flight per ctx
+    bool pending = false;
+    hipStream_t pending_stream = nullptr;
+};
+
 // Element size of each pkt_out_t column, in declaration order (slot columns: one slot; the
 // ipv6 addresses: 16 raw bytes).
 constexpr int kNumCols = 49;
@@ -92,6 +105,7 @@ struct pkt_ctx {
     int device;
     HostPipe hp;
     PcapScratch pc;
+    PcapWriteScratch pw;
     MaxScratch mx;
     uint32_t window;  // 0 = auto
     int fast;         // register fast path for Ether/IPv4/UDP|TCP packets

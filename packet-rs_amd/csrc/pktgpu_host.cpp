@@ -125,6 +125,59 @@ int pkt_pcap_index(const uint8_t* buf, uint64_t len, uint64_t* offsets, uint32_t
     return PKT_SUCCESS;
 }
 
+// pkt_pcap_write on host pointers (the CPU model of pktgpu_pcapw.hip): tests/pcap.rs:7-37 over the
+// selected packets of the batch, in batch order.  Two passes: the totals, then the bytes.
+int pkt_pcap_write_host(const pkt_batch_t* b, const uint8_t* select, uint32_t snaplen, uint32_t tv_sec,
+                        uint32_t tv_usec, const uint32_t* ts_sec, const uint32_t* ts_usec, uint8_t* dst, uint64_t dst_len,
+                        uint64_t* rec_offsets, uint32_t* rec_lens, uint32_t* src_index, uint64_t* bytes_out,
+                        uint64_t* n_out) {
+    static const uint8_t kGlobal[24] = {0xD4, 0xC3, 0xB2, 0xA1, 0x2, 0x0, 0x4, 0x0, 0, 0, 0, 0,
+                                        0,    0,    0,    0,    0xFF, 0xFF, 0, 0, 1, 0, 0, 0};
+    if (bytes_out) *bytes_out = 0;
+    if (n_out) *n_out = 0;
+    if (!b || b->n >= (1ull << 32) || (dst_len && !dst)) return PKT_ERR_INVALID_ARG;
+    if (b->n && ((b->slab_len && !b->slab) || (b->offsets && !b->lens) || (!b->offsets && b->stride == 0)))
+        return PKT_ERR_INVALID_ARG;
+    auto pkt = [&](uint64_t i, uint64_t& off, uint32_t& len, uint32_t& incl) {
+        off = b->offsets ? b->offsets[i] : i * b->stride;
+        const uint64_t room = off < b->slab_len ? b->slab_len - off : 0;
+        uint64_t l = b->lens ? b->lens[i] : b->stride;
+        l = l > room ? room : l;
+        len = l > 65535 ? 65535u : (uint32_t)l;
+        incl = snaplen && len > snaplen ? snaplen : len;
+    };
+    uint64_t total = 24, cnt = 0;
+    for (uint64_t i = 0; i < b->n; i++) {
+        if (select && !select[i]) continue;
+        uint64_t off;
+        uint32_t len, incl;
+        pkt(i, off, len, incl);
+        total += 16 + (uint64_t)incl;
+        cnt++;
+    }
+    if (bytes_out) *bytes_out = total;
+    if (n_out) *n_out = cnt;
+    if (total > dst_len) return PKT_ERR_INVALID_ARG;  // the size to retry with is in *bytes_out
+    memcpy(dst, kGlobal, 24);
+    uint64_t pos = 24, k = 0;
+    for (uint64_t i = 0; i < b->n; i++) {
+        if (select && !select[i]) continue;
+        uint64_t off;
+        uint32_t len, incl;
+        pkt(i, off, len, incl);
+        const uint32_t hdr[4] = {ts_sec ? ts_sec[i] : tv_sec, ts_usec ? ts_usec[i] : tv_usec, incl, len};
+        for (int j = 0; j < 4; j++)
+            for (int x = 0; x < 4; x++) dst[pos + 4 * j + x] = (uint8_t)(hdr[j] >> (8 * x));
+        if (incl) memcpy(dst + pos + 16, b->slab + off, incl);
+        if (rec_offsets) rec_offsets[k] = pos + 16;
+        if (rec_lens) rec_lens[k] = incl;
+        if (src_index) src_index[k] = (uint32_t)i;
+        pos += 16 + (uint64_t)incl;
+        k++;
+    }
+    return PKT_SUCCESS;
+}
+
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,
 // packet.rs:724-731: insert / set_payload).
 int pkt_view(const pkt_out_t* out, uint64_t n, uint64_t i, uint8_t types[PKT_MAX_HDRS], uint16_t offs[PKT_MAX_HDRS],

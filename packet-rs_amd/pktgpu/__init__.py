@@ -453,6 +453,82 @@ class Parser:
         k = min(cap, n.value)
         return offs[:k], lens[:k], n.value
 
+    def _pcap_write_args(self, slab, offsets, lens, stride, select, snaplen, ts, dst, index, n=None):
+        """The marshalled arguments shared by pcap_write / pcap_write_async."""
+        torch = _torch()
+        b = self._batch(slab, n, stride, offsets, lens)
+        n = b.n
+        if select is not None:
+            if select.dtype == torch.bool:
+                select = select.view(torch.uint8)
+            assert select.dtype == torch.uint8 and select.is_cuda and select.numel() == n
+        tv, tsp = [0, 0], [None, None]
+        for k in range(2):
+            if isinstance(ts[k], int):
+                tv[k] = ts[k]
+            else:
+                assert ts[k].dtype == torch.uint32 and ts[k].is_cuda and ts[k].numel() == n
+                tsp[k] = ts[k]
+        if dst is None:
+            # the exact bound: 24 + 16 n + the packets' lengths, each capped as the kernel caps it
+            cap = min(65535, int(snaplen)) if snaplen else 65535
+            if lens is None:
+                data = n * min(int(stride), cap)
+            else:
+                data = int(lens[:n].view(torch.int32).to(torch.int64).bitwise_and_(0xFFFFFFFF).clamp_(max=cap).sum().item()) if n else 0
+            dst = torch.empty(24 + 16 * n + data, dtype=torch.uint8, device=self.torch_device)
+        assert dst.dtype == torch.uint8 and dst.is_cuda and dst.is_contiguous()
+        rec = (None, None, None)
+        if index:
+            rec = (torch.empty(n, dtype=torch.uint64, device=self.torch_device),
+                   torch.empty(n, dtype=torch.uint32, device=self.torch_device),
+                   torch.empty(n, dtype=torch.uint32, device=self.torch_device))
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        args = (ctypes.byref(b), ptr(select), int(snaplen), tv[0], tv[1], ptr(tsp[0]), ptr(tsp[1]),
+                ptr(dst), dst.numel(), ptr(rec[0]), ptr(rec[1]), ptr(rec[2]))
+        return args, dst, rec, (b, select, tsp)
+
+    def _pcap_write_done(self, rc, what, total, n, dst, rec):
+        if rc != 0 and total > dst.numel():
+            raise RuntimeError(f"{what}: dst holds {dst.numel()} bytes, the capture needs {total} "
+                               f"({n} records)")
+        self._check(rc, what)
+        return (dst[:total], n) + tuple(r[:n] if r is not None else None for r in rec)
+
+    def pcap_write(self, slab, offsets=None, lens=None, stride=None, select=None, snaplen=0, ts=(0, 0),
+                   dst=None, index=True, stream=None, n=None):
+        """pkt_pcap_write: the selected packets of a device batch (fixed `stride`, or `offsets` / `lens`)
+        as one tests/pcap.rs capture in device memory -> (capture, n, offsets, lens, src_index).
+        `capture` is a uint8 view of exactly the bytes written; `select` a uint8 / bool device tensor
+        [n] or None (all); `snaplen` 0 = whole packets; `ts` = (sec, usec), each an int (one time for
+        the file) or a uint32 device tensor indexed by source packet.  dst=None allocates the exact
+        upper bound (the device sum of `lens` for an indexed batch); a caller's `dst` that is too
+        small raises with the size needed.  index=True also returns the written records' (data
+        offset, incl_len) — with `capture` an indexed batch — and their source packet indices."""
+        args, dst, rec, keep = self._pcap_write_args(slab, offsets, lens, stride, select, snaplen, ts, dst, index, n)
+        total, n = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self._L.pkt_pcap_write(self._ctx, *args, ctypes.byref(total), ctypes.byref(n), self._stream(stream))
+        return self._pcap_write_done(rc, "pkt_pcap_write", total.value, n.value, dst, rec)
+
+    def pcap_write_async(self, slab, offsets=None, lens=None, stride=None, select=None, snaplen=0, ts=(0, 0),
+                         dst=None, index=True, stream=None, n=None):
+        """pkt_pcap_write_async: queue pcap_write on `stream` without waiting for its totals (pass
+        `dst`: sizing one for an indexed batch waits for the sum of `lens`).  pcap_write_result()
+        waits and returns pcap_write's tuple; one write in flight per Parser."""
+        args, dst, rec, keep = self._pcap_write_args(slab, offsets, lens, stride, select, snaplen, ts, dst, index, n)
+        self._check(self._L.pkt_pcap_write_async(self._ctx, *args, self._stream(stream)), "pkt_pcap_write_async")
+        self._pcap_write_queued = (dst, rec, keep, (slab, offsets, lens))
+
+    def pcap_write_result(self):
+        """pkt_pcap_write_result: waits for the queued pcap_write_async -> pcap_write's tuple."""
+        total, n = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self._L.pkt_pcap_write_result(self._ctx, ctypes.byref(total), ctypes.byref(n))
+        q = self.__dict__.pop("_pcap_write_queued", None)
+        if q is None:
+            self._check(rc, "pkt_pcap_write_result")
+            raise RuntimeError("pcap_write_result: no write queued")
+        return self._pcap_write_done(rc, "pkt_pcap_write_result", total.value, n.value, q[0], q[1])
+
     def pcap_index_device_timed(self, buf, offsets, lens, stream=None):
         """pkt_pcap_index_device_timed into the caller's device `offsets` / `lens` (cap = their
         length): (record count, [guess, scan, emit] kernel ms from HIP events between them)."""
@@ -480,6 +556,60 @@ def pcap_index(buf):
     if rc != 0:
         raise ValueError("bad pcap")
     return offs, lens
+
+
+def pcap_write(slab, offsets=None, lens=None, stride=None, select=None, snaplen=0, ts=(0, 0), dst=None,
+               n=None):
+    """pkt_pcap_write_host over numpy arrays (no device): the selected packets of a host batch as a
+    tests/pcap.rs capture -> (capture uint8, n, offsets uint64, lens uint32, src_index uint32).
+    Arguments as Parser.pcap_write, with numpy arrays; `dst` (uint8, optional) receives the bytes,
+    and one that is too small raises with the size needed."""
+    from . import _lib
+    L = _lib.load()
+    slab = np.ascontiguousarray(slab, np.uint8).reshape(-1)
+    b = _lib.PktBatch()
+    b.slab = slab.ctypes.data if slab.size else None
+    b.slab_len = slab.size
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        lens = np.ascontiguousarray(lens, np.uint32)
+        n = offsets.size if n is None else n
+        b.offsets = offsets.ctypes.data if n else None
+    else:
+        n = slab.size // stride if n is None else n
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, np.uint32)
+    if lens is not None:
+        b.lens = lens.ctypes.data if n else None
+    b.stride = stride or 0
+    b.n = int(n)
+    if select is not None:
+        select = np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+        assert select.size == n
+    tv, tsp = [0, 0], [None, None]
+    for k in range(2):
+        if isinstance(ts[k], (int, np.integer)):
+            tv[k] = int(ts[k])
+        else:
+            tsp[k] = np.ascontiguousarray(ts[k], np.uint32)
+            assert tsp[k].size == n
+    if dst is None:
+        cap = min(65535, int(snaplen)) if snaplen else 65535
+        data = n * min(int(stride), cap) if lens is None else int(np.minimum(lens[:n].astype(np.int64), cap).sum())
+        dst = np.empty(24 + 16 * n + data, np.uint8)
+    assert dst.dtype == np.uint8 and dst.flags.c_contiguous
+    ro, rl, si = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    total, cnt = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = L.pkt_pcap_write_host(ctypes.byref(b), ptr(select), int(snaplen), tv[0], tv[1], ptr(tsp[0]), ptr(tsp[1]),
+                               ptr(dst), dst.size, ptr(ro), ptr(rl), ptr(si), ctypes.byref(total), ctypes.byref(cnt))
+    if rc != 0 and total.value > dst.size:
+        raise ValueError(f"pcap_write: dst holds {dst.size} bytes, the capture needs {total.value} "
+                         f"({cnt.value} records)")
+    if rc != 0:
+        raise ValueError(f"pkt_pcap_write_host failed ({rc})")
+    k = cnt.value
+    return dst[:total.value], k, ro[:k], rl[:k], si[:k]
 
 
 # ----------------------------------------------------------------- PacketSlice-style host views

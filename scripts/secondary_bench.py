@@ -9,6 +9,9 @@
   to_vec_c2 / to_vec_c4   PacketSlice::to_vec of every parsed packet (tests/lib.rs:790-817), C2 slab
                  and C4 pcap replay, into the input's layout; to_vec_c4_packed: the C4 outputs
                  packed back to back (dst_offsets = prefix of the lengths)
+  pcap_write     pkt_pcap_write (tests/pcap.rs:7-37 as a batch operation), two lines: pcap_write_c2, the
+                 C2 slab at fixed stride with every packet selected, and pcap_write_c4, an indexed batch
+                 over a C4 capture with every record selected (the capture again); timed per call
   extract_c2     every field of Ether/IPv4/UDP (19 specs, one launch) over C2 (headers.rs:195-201)
   setfields_c2   4 setters + the IPv4 checksum refresh, in place over C2 (headers.rs:315-324)
 
@@ -288,6 +291,68 @@ def main():
               "dst": "packed: dst_offsets = prefix of the lengths"})
         del dstp
         del dsts, d4
+    if want("pcap_write"):
+        import ctypes
+
+        def write_ms(slab, total, **kw):
+            """GPU time of one pkt_pcap_write_async call (its four kernels), HIP events around each
+            call, the result taken (one write in flight per ctx) before the next; the arguments are
+            marshalled before the first event.  Destinations from a >= 1 GiB ring."""
+            ring_w = max(2, (1 << 30) // total + 1)
+            dsts = [torch.empty(total, dtype=torch.uint8, device=dev) for _ in range(ring_w)]
+            nn = kw["offsets"].numel() if kw.get("offsets") is not None else slab.numel() // kw["stride"]
+            rec = (torch.empty(nn, dtype=torch.uint64, device=dev), torch.empty(nn, dtype=torch.uint32, device=dev),
+                   torch.empty(nn, dtype=torch.uint32, device=dev))
+            b = P._batch(slab, None, kw.get("stride"), kw.get("offsets"), kw.get("lens"))
+            s, tb, tn = P._stream(None), ctypes.c_uint64(), ctypes.c_uint64()
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(it)]
+            cur = torch.cuda.current_stream()
+            for k in range(-3, it):
+                if k >= 0:
+                    evs[k][0].record(cur)
+                rc = P._L.pkt_pcap_write_async(P._ctx, ctypes.byref(b), None, 0, 0, 0, None, None,
+                                               dsts[k % ring_w].data_ptr(), total, rec[0].data_ptr(), rec[1].data_ptr(),
+                                               rec[2].data_ptr(), s)
+                if k >= 0:
+                    evs[k][1].record(cur)
+                assert rc == 0 and P._L.pkt_pcap_write_result(P._ctx, ctypes.byref(tb), ctypes.byref(tn)) == 0
+                assert tb.value == total and tn.value == nn
+            torch.cuda.synchronize()
+            t = sorted(a.elapsed_time(z) for a, z in evs)
+            return sum(t) / len(t), t[len(t) // 2], t[0]
+
+        def write_cpu(slab_h, m, **kw):
+            r, t = timed(lambda: pktgpu.pcap_write(slab_h, **kw), args.cpu_budget)
+            return {"value": round(r * m / t / 1e9, 6), "unit": "Gpkt/s", "cores": 1, "kind": "port",
+                    "sample": f"{r} x {m} packets of pkt_pcap_write_host (the CPU model: a header and a memcpy per "
+                              "record, tests/pcap.rs:26-36), 1 thread"}
+
+        how = {"measured": "mean over the iterations of HIP events around ONE call's four kernels (reduce, scan, "
+                           "emit, copy), the write's result taken between calls; dst from a >= 1 GiB ring"}
+        # (a) the C2 slab, fixed stride, every packet: 64 B read; 16 + 64 B of file and the record table written
+        tot2 = 24 + n * 80
+        ms, med, best = write_ms(slabs[0], tot2, stride=64)
+        cap, m_, o_, l_, s_ = P.pcap_write(slabs[0], stride=64)
+        ok = cap[:24 + 4096 * 80].cpu().numpy().tobytes() == gen.pcap_bytes([c2[64 * i:64 * i + 64].tobytes() for i in range(4096)])
+        ok = ok and m_ == n and cap.numel() == tot2 and bool((s_.cpu().numpy() == np.arange(n)).all())
+        cpu_m = 1 << 18
+        line("pcap_write_c2", n, ms, 64, 80 + 16, write_cpu(c2[:cpu_m * 64], cpu_m, stride=64),
+             dict(how, parity_vs_struct_pack_first_4096=bool(ok), capture_bytes=tot2,
+                  median_us=round(med * 1e3, 2), min_us=round(best * 1e3, 2)))
+        del cap
+        # (b) an indexed batch over a C4 capture, every record: the capture again
+        s4, o4, l4 = gen.gen_c4(n)
+        d4, do4, dl4 = torch.from_numpy(s4).to(dev), torch.from_numpy(o4).to(dev), torch.from_numpy(l4).to(dev)
+        ms, med, best = write_ms(d4, s4.size, offsets=do4, lens=dl4)
+        cap, m_, o_, l_, s_ = P.pcap_write(d4, offsets=do4, lens=dl4)
+        ok = m_ == n and bool(torch.equal(cap, d4)) and np.array_equal(o_.cpu().numpy(), o4)
+        avg = float(l4.mean())
+        cpu_m = 1 << 17
+        line("pcap_write_c4", n, ms, round(avg + 8 + 4, 1), round(avg + 16 + 16, 1),
+             write_cpu(s4, cpu_m, offsets=o4[:cpu_m], lens=l4[:cpu_m]),
+             dict(how, parity_reproduces_the_capture=bool(ok), capture_bytes=int(s4.size), avg_record_bytes=round(avg, 1),
+                  median_us=round(med * 1e3, 2), min_us=round(best * 1e3, 2)))
+        del cap, d4
     if want("extract_c2"):
         from pktgpu import fields as F
         specs = [(h, 0, s0, e0) for h in ("Ether", "IPv4", "UDP") for (s0, e0) in F.FIELDS[schema.HDR_ID[h]].values()]
