@@ -224,6 +224,23 @@ class Parser {
         return total;
     }
 
+    // Packet::compare (packet.rs:326-358) over two device batches: packet i of `a` against packet i of
+    // `b` (raw bytes on both sides: run to_vec first for the reference's to_vec order).  result[i] =
+    // PKT_CMP_EQUAL / _LEN / _BYTES, matching[i] = the equal positions of the common bytes, first_diff[i]
+    // = the first unequal one; device arrays of n, each may be NULL.  `ignore` (at most 16 specs, with
+    // chain_a = the chain columns of a parse of `a`) names bit ranges that never count as a difference.
+    // Returns the summary: packets per result and the lowest index that is not equal (n if none).
+    pkt_cmp_summary_t compare(const pkt_batch_t& a, const pkt_batch_t& b, uint8_t* result = nullptr,
+                              uint32_t* matching = nullptr, uint32_t* first_diff = nullptr,
+                              const std::vector<pkt_field_spec_t>& ignore = {}, const pkt_chain_t* chain_a = nullptr,
+                              hipStream_t s = nullptr) {
+        pkt_cmp_summary_t sm{};
+        check(pkt_compare_batch(ctx_, &a, &b, chain_a, ignore.data(), (uint32_t)ignore.size(), result, matching,
+                                first_diff, &sm, s),
+              ctx_, "pkt_compare_batch");
+        return sm;
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

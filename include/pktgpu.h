@@ -544,6 +544,57 @@ int pkt_pcap_write_host(const pkt_batch_t *batch, const uint8_t *select, uint32_
                         uint64_t dst_len, uint64_t *rec_offsets, uint32_t *rec_lens, uint32_t *src_index,
                         uint64_t *bytes_out, uint64_t *n_out);
 
+/* ---- comparing two batches ----
+ * Packet::compare / compare_with_slice (packet.rs:326-358) as a batch operation: packet i of `a`
+ * against packet i of `b`.  la, lb = the two packets' lengths under the pkt_batch_t rules (clamped to
+ * the slab end and to 65535), m = min(la, lb).
+ *  - byte j < m MATCHES iff ((a[j] ^ b[j]) & ~ign[j]) == 0 (ign = the packet's ignore mask, below).
+ *  - matching[i]   = the number of matching j in [0, m): the reference's zip/filter/count
+ *    (packet.rs:347), a count of equal positions and not a prefix length.
+ *  - first_diff[i] = the smallest non-matching j, or m when there is none (an extension: the reference
+ *    prints only the count).
+ *  - result[i]     = PKT_CMP_LEN if la != lb (the reference's first test, packet.rs:342: decided
+ *    before any byte, never changed by the ignores), else PKT_CMP_BYTES if matching != la, else
+ *    PKT_CMP_EQUAL.  For PKT_CMP_LEN, matching and first_diff still cover the common m bytes (a
+ *    snaplen-cut capture shows matching == m).
+ *  - ignore: up to 16 specs, resolved per packet against chain_a, the chain columns of a parse of
+ *    `a`.  Spec (hdr_type, occurrence, start, end) ignores bits [start..=end] (MSB-first from the
+ *    header's first byte, as pkt_extract_fields; any width end >= start) of that header of packet i's
+ *    own chain, in a[i] and at the same bit positions in b[i].  Bits at or past 8 m are dropped; a
+ *    packet whose chain lacks the header (n_hdrs == 0 included) ignores nothing for that spec; specs
+ *    may overlap.  nignore == 0 needs no chain.
+ *  - a, b: any two pkt_batch_t, fixed-stride or indexed in any mix, under the usual slab rules; both
+ *    are only read and may overlap or be the same buffer.  result / matching / first_diff: device
+ *    [n], each may be NULL.  summary (host) may be NULL.
+ *  - PKT_ERR_INVALID_ARG: a->n != b->n, n >= 2^32, nignore > 16, nignore > 0 with a NULL chain, a spec
+ *    with end < start.  n == 0 succeeds with an all-zero summary (first_bad = 0).
+ * The reference's compare is self.to_vec() against the other's bytes; here BOTH sides are the raw
+ * batch bytes.  A caller who wants the to_vec order (a packet with two or more GRE options, Q2) runs
+ * pkt_to_vec_batch first and compares its output.
+ * pkt_compare_batch is blocking: one host wait, for the summary (work is ordered on `stream`).
+ * pkt_compare_batch_async queues the same work and returns; the summary goes to pinned words of the
+ * ctx and pkt_compare_result waits for them.  One compare in flight per ctx: another compare on the
+ * ctx before the result is taken fails with PKT_ERR_INVALID_ARG.  pkt_compare_host is the same
+ * operation on HOST pointers and needs no device or ctx. */
+typedef enum pkt_cmp { PKT_CMP_EQUAL = 0, PKT_CMP_LEN = 1, PKT_CMP_BYTES = 2 } pkt_cmp_t;
+typedef struct pkt_cmp_summary {
+    uint64_t n_equal;    /* packets per result; the three sum to n */
+    uint64_t n_len;
+    uint64_t n_bytes;
+    uint64_t first_bad;  /* lowest i with result != PKT_CMP_EQUAL, n if none */
+} pkt_cmp_summary_t;
+size_t pkt_sizeof_cmp_summary(void);
+int pkt_compare_batch(pkt_ctx_t *ctx, const pkt_batch_t *a, const pkt_batch_t *b, const pkt_chain_t *chain_a,
+                      const pkt_field_spec_t *ignore, uint32_t nignore, uint8_t *result, uint32_t *matching,
+                      uint32_t *first_diff, pkt_cmp_summary_t *summary, void *stream);
+int pkt_compare_batch_async(pkt_ctx_t *ctx, const pkt_batch_t *a, const pkt_batch_t *b,
+                            const pkt_chain_t *chain_a, const pkt_field_spec_t *ignore, uint32_t nignore,
+                            uint8_t *result, uint32_t *matching, uint32_t *first_diff, void *stream);
+int pkt_compare_result(pkt_ctx_t *ctx, pkt_cmp_summary_t *summary);
+int pkt_compare_host(const pkt_batch_t *a, const pkt_batch_t *b, const pkt_chain_t *chain_a,
+                     const pkt_field_spec_t *ignore, uint32_t nignore, uint8_t *result, uint32_t *matching,
+                     uint32_t *first_diff, pkt_cmp_summary_t *summary);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -946,6 +946,12 @@ int pkt_ctx_destroy(pkt_ctx_t* ctx) {
         (void)hipFree(ctx->pw.buf);
         (void)hipHostFree(ctx->pw.ctl);
     }
+    if (ctx && (ctx->cmp.acc || ctx->cmp.ctl)) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(ctx->cmp.acc);
+        (void)hipHostFree(ctx->cmp.ctl);
+    }
     if (ctx && ctx->hp.init) {
         (void)hipSetDevice(ctx->device);
         for (int k = 0; k < HostPipe::kSlots; k++) {

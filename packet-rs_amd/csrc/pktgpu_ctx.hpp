@@ -68,6 +68,19 @@ struct PcapWriteScratch {
     hipStream_t pending_stream = nullptr;
 };
 
+// Scratch of pkt_compare_batch (pktgpu_compare.hip): 256 slots of four device words the blocks add
+// their counts to (equal, len, bytes; the lowest bad index as the maximum of its complement), all zero
+// between calls, and the pinned words their sums are copied to.
+struct CompareScratch {
+    uint64_t* acc = nullptr;      // device: the slots
+    uint64_t* ctl = nullptr;      // pinned host words: [n_equal, n_len, n_bytes, first_bad (~0: none)]
+    uint64_t* ctl_dev = nullptr;  // the same words as the device addresses them
+    uint64_t n = 0;               // the last queued compare's n (first_bad when every pair is equal)
+    // a compare queued by pkt_compare_batch_async whose result has not been taken: one in flight per ctx
+    bool pending = false;
+    hipStream_t pending_stream = nullptr;
+};
+
 // Element size of each pkt_out_t column, in declaration order (slot columns: one slot; the
 // ipv6 addresses: 16 raw bytes).
 constexpr int kNumCols = 49;
@@ -106,6 +119,7 @@ struct pkt_ctx {
     HostPipe hp;
     PcapScratch pc;
     PcapWriteScratch pw;
+    CompareScratch cmp;
     MaxScratch mx;
     uint32_t window;  // 0 = auto
     int fast;         // register fast path for Ether/IPv4/UDP|TCP packets

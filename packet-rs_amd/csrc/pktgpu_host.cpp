@@ -1,6 +1,7 @@
 // pktgpu_host.cpp — host-side part of the C ABI: metadata tables, the pcap indexer and the
 // host checksum.  No device code.
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/pktgpu.h"
 
@@ -86,6 +87,7 @@ int pkt_abi_version(void) { return PKTGPU_ABI_VERSION; }
 size_t pkt_sizeof_batch(void) { return sizeof(pkt_batch_t); }
 size_t pkt_sizeof_out(void) { return sizeof(pkt_out_t); }
 size_t pkt_sizeof_field_spec(void) { return sizeof(pkt_field_spec_t); }
+size_t pkt_sizeof_cmp_summary(void) { return sizeof(pkt_cmp_summary_t); }
 
 const char* pkt_hdr_name(int t) { return (t > 0 && t < PKT_HDR_COUNT) ? kHdrs[t].name : nullptr; }
 int pkt_hdr_size(int t) { return (t > 0 && t < PKT_HDR_COUNT) ? kHdrs[t].size : 0; }
@@ -175,6 +177,73 @@ int pkt_pcap_write_host(const pkt_batch_t* b, const uint8_t* select, uint32_t sn
         pos += 16 + (uint64_t)incl;
         k++;
     }
+    return PKT_SUCCESS;
+}
+
+// pkt_compare_batch on host pointers (the CPU model of pktgpu_compare.hip): Packet::compare
+// (packet.rs:326-358) of packet i of `a` against packet i of `b`, byte by byte.
+int pkt_compare_host(const pkt_batch_t* a, const pkt_batch_t* b, const pkt_chain_t* chain, const pkt_field_spec_t* ignore,
+                     uint32_t nignore, uint8_t* result, uint32_t* matching, uint32_t* first_diff,
+                     pkt_cmp_summary_t* summary) {
+    if (summary) *summary = pkt_cmp_summary_t{0, 0, 0, 0};
+    if (!a || !b || a->n != b->n || a->n >= (1ull << 32) || nignore > 16) return PKT_ERR_INVALID_ARG;
+    if (nignore && (!ignore || !chain || !chain->n_hdrs || !chain->hdr_type || !chain->hdr_off)) return PKT_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < nignore; k++)
+        if (ignore[k].end < ignore[k].start) return PKT_ERR_INVALID_ARG;
+    const uint64_t n = a->n;
+    for (const pkt_batch_t* s : {a, b})
+        if (n && ((s->slab_len && !s->slab) || (s->offsets && !s->lens) || (!s->offsets && s->stride == 0)))
+            return PKT_ERR_INVALID_ARG;
+    auto pkt = [](const pkt_batch_t* s, uint64_t i, uint32_t& len) -> const uint8_t* {
+        const uint64_t off = s->offsets ? s->offsets[i] : i * s->stride;
+        const uint64_t room = off < s->slab_len ? s->slab_len - off : 0;
+        uint64_t l = s->lens ? s->lens[i] : s->stride;
+        l = l > room ? room : l;
+        len = l > 65535 ? 65535u : (uint32_t)l;
+        return len ? s->slab + off : nullptr;
+    };
+    pkt_cmp_summary_t sum{0, 0, 0, n};
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t la, lb;
+        const uint8_t* pa = pkt(a, i, la);
+        const uint8_t* pb = pkt(b, i, lb);
+        const uint32_t m = la < lb ? la : lb;
+        // the specs' bit ranges in packet i, first > last where its chain lacks the header
+        uint32_t lo[16], hi[16];
+        for (uint32_t k = 0; k < nignore; k++) {
+            lo[k] = 1, hi[k] = 0;
+            uint32_t nh = chain->n_hdrs[i], seen = 0;
+            nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+            for (uint32_t j = 0; j < nh; j++) {
+                if (chain->hdr_type[j * n + i] != ignore[k].hdr_type) continue;
+                if (seen++ == ignore[k].occurrence) {
+                    lo[k] = 8u * chain->hdr_off[j * n + i] + ignore[k].start;
+                    hi[k] = 8u * chain->hdr_off[j * n + i] + ignore[k].end;
+                    break;
+                }
+            }
+        }
+        uint32_t cnt = 0, fd = m;
+        for (uint32_t j = 0; j < m; j++) {
+            uint8_t d = pa[j] ^ pb[j];
+            for (uint32_t k = 0; d && k < nignore; k++) {
+                if (lo[k] > hi[k] || hi[k] < 8u * j || lo[k] > 8u * j + 7u) continue;
+                const uint32_t l = lo[k] > 8u * j ? lo[k] - 8u * j : 0u, h = hi[k] < 8u * j + 7u ? hi[k] - 8u * j : 7u;
+                d &= (uint8_t)~((0xFFu >> l) & (0xFFu << (7u - h)));  // bit t of the byte, MSB-first
+            }
+            if (!d)
+                cnt++;
+            else if (fd == m)
+                fd = j;
+        }
+        const uint8_t r = la != lb ? PKT_CMP_LEN : cnt != la ? PKT_CMP_BYTES : PKT_CMP_EQUAL;
+        if (result) result[i] = r;
+        if (matching) matching[i] = cnt;
+        if (first_diff) first_diff[i] = fd;
+        (r == PKT_CMP_EQUAL ? sum.n_equal : r == PKT_CMP_LEN ? sum.n_len : sum.n_bytes)++;
+        if (r != PKT_CMP_EQUAL && sum.first_bad == n) sum.first_bad = i;
+    }
+    if (summary) *summary = sum;
     return PKT_SUCCESS;
 }
 

@@ -529,6 +529,58 @@ class Parser:
             raise RuntimeError("pcap_write_result: no write queued")
         return self._pcap_write_done(rc, "pkt_pcap_write_result", total.value, n.value, q[0], q[1])
 
+    def _compare_args(self, a, b, ignore, chain, outputs=True):
+        """The marshalled arguments shared by compare / compare_async."""
+        torch = _torch()
+        ba, bb = (self._batch(d["slab"], d.get("n"), d.get("stride"), d.get("offsets"), d.get("lens")) for d in (a, b))
+        n = ba.n
+        sp, k = _cmp_specs(self._lib, ignore)
+        if k and chain is None:
+            raise ValueError("compare: ignore needs the chain columns of a parse of `a`")
+        ch = self._chain(chain) if chain is not None else None
+        out = (None, None, None)
+        if outputs:
+            out = (torch.empty(n, dtype=torch.uint8, device=self.torch_device),
+                   torch.empty(n, dtype=torch.uint32, device=self.torch_device),
+                   torch.empty(n, dtype=torch.uint32, device=self.torch_device))
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        args = (ctypes.byref(ba), ctypes.byref(bb), ctypes.byref(ch) if ch is not None else None, sp, k,
+                ptr(out[0]), ptr(out[1]), ptr(out[2]))
+        return args, out, (ba, bb, ch, sp)
+
+    def compare(self, a, b, ignore=(), chain=None, stream=None):
+        """pkt_compare_batch: Packet::compare of packet i of `a` against packet i of `b` ->
+        (result uint8, matching uint32, first_diff uint32, summary dict).  `a`, `b`: dicts with the
+        batch's `slab` and `stride` or `offsets` / `lens` (optionally `n`), fixed-stride or indexed in
+        any mix.  result: 0 equal, 1 the lengths differ, 2 bytes differ (pktgpu.CMP_*); matching =
+        the number of equal positions of the common bytes, first_diff = the first unequal one (the
+        common length if none).  `ignore` = up to 16 (hdr_type|name, occurrence, start, end) bit
+        ranges, as for extract_fields, resolved per packet against `chain`, the chain columns of a
+        parse of `a`; their bits never count as a difference.  Both sides are raw bytes: run to_vec
+        first for the reference's to_vec order."""
+        args, out, keep = self._compare_args(a, b, ignore, chain)
+        sm = self._lib.PktCmpSummary()
+        self._check(self._L.pkt_compare_batch(self._ctx, *args, ctypes.byref(sm), self._stream(stream)),
+                    "pkt_compare_batch")
+        return out + (_cmp_summary(sm),)
+
+    def compare_async(self, a, b, ignore=(), chain=None, stream=None):
+        """pkt_compare_batch_async: queue compare on `stream` without waiting for its summary.
+        compare_result() waits and returns compare's tuple; one compare in flight per Parser."""
+        args, out, keep = self._compare_args(a, b, ignore, chain)
+        self._check(self._L.pkt_compare_batch_async(self._ctx, *args, self._stream(stream)), "pkt_compare_batch_async")
+        self._compare_queued = (out, keep, (a, b, chain))
+
+    def compare_result(self):
+        """pkt_compare_result: waits for the queued compare_async -> compare's tuple."""
+        sm = self._lib.PktCmpSummary()
+        rc = self._L.pkt_compare_result(self._ctx, ctypes.byref(sm))
+        q = self.__dict__.pop("_compare_queued", None)
+        self._check(rc, "pkt_compare_result")
+        if q is None:
+            raise RuntimeError("compare_result: no compare queued")
+        return q[0] + (_cmp_summary(sm),)
+
     def pcap_index_device_timed(self, buf, offsets, lens, stream=None):
         """pkt_pcap_index_device_timed into the caller's device `offsets` / `lens` (cap = their
         length): (record count, [guess, scan, emit] kernel ms from HIP events between them)."""
@@ -610,6 +662,68 @@ def pcap_write(slab, offsets=None, lens=None, stride=None, select=None, snaplen=
         raise ValueError(f"pkt_pcap_write_host failed ({rc})")
     k = cnt.value
     return dst[:total.value], k, ro[:k], rl[:k], si[:k]
+
+
+CMP_EQUAL, CMP_LEN, CMP_BYTES = 0, 1, 2
+
+
+def _cmp_specs(lib, ignore):
+    k = len(ignore)
+    sp = (lib.PktFieldSpec * max(1, k))()
+    for i, (t, occ, s, e) in enumerate(ignore):
+        t = HDR_ID[t] if isinstance(t, str) else int(t)
+        sp[i] = lib.PktFieldSpec(t, occ, s, e, 0)
+    return sp, k
+
+
+def _cmp_summary(sm):
+    return {"n_equal": sm.n_equal, "n_len": sm.n_len, "n_bytes": sm.n_bytes, "first_bad": sm.first_bad}
+
+
+def _host_batch(lib, d):
+    """A PktBatch over the numpy arrays of a batch dict (and the arrays, to keep them alive)."""
+    slab = np.ascontiguousarray(d["slab"], np.uint8).reshape(-1)
+    offsets, lens, stride, n = d.get("offsets"), d.get("lens"), d.get("stride"), d.get("n")
+    b = lib.PktBatch()
+    b.slab = slab.ctypes.data if slab.size else None
+    b.slab_len = slab.size
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        lens = np.ascontiguousarray(lens, np.uint32)
+        n = offsets.size if n is None else n
+        b.offsets = offsets.ctypes.data if n else None
+    else:
+        n = slab.size // stride if n is None else n
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, np.uint32)
+    if lens is not None:
+        b.lens = lens.ctypes.data if n else None
+    b.stride = stride or 0
+    b.n = int(n)
+    return b, (slab, offsets, lens)
+
+
+def compare(a, b, ignore=(), chain=None):
+    """pkt_compare_host over numpy arrays (no device): Parser.compare's arguments with numpy arrays
+    in the batch dicts and in `chain` -> (result uint8, matching uint32, first_diff uint32, summary)."""
+    from . import _lib
+    L = _lib.load()
+    (ba, keep_a), (bb, keep_b) = _host_batch(_lib, a), _host_batch(_lib, b)
+    n = ba.n
+    sp, k = _cmp_specs(_lib, ignore)
+    ch = None
+    if chain is not None:
+        cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                np.ascontiguousarray(chain["hdr_off"], np.uint16))
+        ch = _lib.PktChain(*[c.ctypes.data for c in cols])
+    res, mt, fd = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    sm = _lib.PktCmpSummary()
+    ptr = lambda x: x.ctypes.data if x.size else None  # noqa: E731
+    rc = L.pkt_compare_host(ctypes.byref(ba), ctypes.byref(bb), ctypes.byref(ch) if ch is not None else None, sp, k,
+                            ptr(res), ptr(mt), ptr(fd), ctypes.byref(sm))
+    if rc != 0:
+        raise ValueError(f"pkt_compare_host failed ({rc})")
+    return res, mt, fd, _cmp_summary(sm)
 
 
 # ----------------------------------------------------------------- PacketSlice-style host views

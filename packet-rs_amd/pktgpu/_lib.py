@@ -37,6 +37,11 @@ class PktFieldSpec(ctypes.Structure):
                 ("reserved", ctypes.c_uint16)]
 
 
+class PktCmpSummary(ctypes.Structure):
+    _fields_ = [("n_equal", ctypes.c_uint64), ("n_len", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64),
+                ("first_bad", ctypes.c_uint64)]
+
+
 class PktGatherPiece(ctypes.Structure):
     _fields_ = [("src", ctypes.c_uint64), ("dst", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
                 ("shard", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
@@ -127,6 +132,17 @@ SIGNATURES = {
     "pkt_pcap_write_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), _P, ctypes.c_uint32, ctypes.c_uint32,
                                            ctypes.c_uint32, _P, _P, _P, ctypes.c_uint64, _P, _P, _P,
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_sizeof_cmp_summary": (ctypes.c_size_t, []),
+    "pkt_compare_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktBatch),
+                                         ctypes.POINTER(PktChain), ctypes.POINTER(PktFieldSpec), ctypes.c_uint32,
+                                         _P, _P, _P, ctypes.POINTER(PktCmpSummary), _P]),
+    "pkt_compare_batch_async": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktBatch),
+                                               ctypes.POINTER(PktChain), ctypes.POINTER(PktFieldSpec),
+                                               ctypes.c_uint32, _P, _P, _P, _P]),
+    "pkt_compare_result": (ctypes.c_int, [_P, ctypes.POINTER(PktCmpSummary)]),
+    "pkt_compare_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktBatch),
+                                        ctypes.POINTER(PktChain), ctypes.POINTER(PktFieldSpec), ctypes.c_uint32,
+                                        _P, _P, _P, ctypes.POINTER(PktCmpSummary)]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -198,7 +214,8 @@ def load():
     if L.pkt_sizeof_out() != ctypes.sizeof(PktOut) or L.pkt_sizeof_batch() != ctypes.sizeof(PktBatch) \
             or L.pkt_sizeof_field_spec() != ctypes.sizeof(PktFieldSpec) \
             or L.pkt_sizeof_gen_field() != ctypes.sizeof(PktGenField) \
-            or L.pkt_sizeof_gather_piece() != ctypes.sizeof(PktGatherPiece):
+            or L.pkt_sizeof_gather_piece() != ctypes.sizeof(PktGatherPiece) \
+            or L.pkt_sizeof_cmp_summary() != ctypes.sizeof(PktCmpSummary):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L
     return L

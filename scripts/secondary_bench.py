@@ -12,6 +12,12 @@
   pcap_write     pkt_pcap_write (tests/pcap.rs:7-37 as a batch operation), two lines: pcap_write_c2, the
                  C2 slab at fixed stride with every packet selected, and pcap_write_c4, an indexed batch
                  over a C4 capture with every record selected (the capture again); timed per call
+  compare        pkt_compare_batch (Packet::compare, packet.rs:326-358, as a batch operation), five lines:
+                 compare_c2, the C2 slab at fixed stride against an identical copy, and compare_pcap, the same
+                 packets against their own pkt_pcap_write capture (an indexed b, misaligned by the 16-byte
+                 record headers), each with no ignores and (_ign4) with 4 IPv4 fields ignored, and
+                 compare_c2_rewritten_ign4, a copy that differs in those 4 fields in every packet; timed
+                 per call; compare_c2 also beside the torch expression a user can write today
   extract_c2     every field of Ether/IPv4/UDP (19 specs, one launch) over C2 (headers.rs:195-201)
   setfields_c2   4 setters + the IPv4 checksum refresh, in place over C2 (headers.rs:315-324)
 
@@ -353,6 +359,76 @@ def main():
              dict(how, parity_reproduces_the_capture=bool(ok), capture_bytes=int(s4.size), avg_record_bytes=round(avg, 1),
                   median_us=round(med * 1e3, 2), min_us=round(best * 1e3, 2)))
         del cap, d4
+    if want("compare"):
+        import ctypes
+        from pktgpu import fields as F
+        ign4 = [("IPv4", 0) + tuple(F.FIELDS[schema.HDR_ID["IPv4"]][f])
+                for f in ("identification", "ttl", "header_checksum", "diffserv")]
+        # a ring of 4 (a, b) pairs: 512 MiB or more read before a pair comes round again
+        caps = [P.pcap_write(s_, stride=64) for s_ in slabs]
+        copies = [s_.clone() for s_ in slabs]
+        outs3 = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint32, device=dev),
+                 torch.empty(n, dtype=torch.uint32, device=dev))
+
+        def compare_ms(bs, ignore):
+            """GPU time of one pkt_compare_batch_async call (the compare kernel and the summary's
+            copy-out), HIP events around each call, the result taken (one compare in flight per ctx)
+            before the next; the arguments are marshalled before the first event."""
+            sp, k = pktgpu._cmp_specs(P._lib, ignore)
+            pa = [P._batch(s_, None, 64, None, None) for s_ in slabs]
+            pb = [P._batch(*x) for x in bs]
+            chs = [P._chain(c_) for c_ in chains]
+            s, sm = P._stream(None), P._lib.PktCmpSummary()
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(it)]
+            cur = torch.cuda.current_stream()
+            for j in range(-3, it):
+                r = j % len(slabs)
+                if j >= 0:
+                    evs[j][0].record(cur)
+                rc = P._L.pkt_compare_batch_async(P._ctx, ctypes.byref(pa[r]), ctypes.byref(pb[r]),
+                                                  ctypes.byref(chs[r]) if k else None, sp, k, outs3[0].data_ptr(),
+                                                  outs3[1].data_ptr(), outs3[2].data_ptr(), s)
+                if j >= 0:
+                    evs[j][1].record(cur)
+                assert rc == 0 and P._L.pkt_compare_result(P._ctx, ctypes.byref(sm)) == 0
+                assert (sm.n_equal, sm.n_len, sm.n_bytes, sm.first_bad) == (n, 0, 0, n)
+            torch.cuda.synchronize()
+            ok = bool((outs3[0] == 0).all()) and bool((outs3[1] == 64).all()) and bool((outs3[2] == 64).all())
+            t = sorted(a.elapsed_time(z) for a, z in evs)
+            return sum(t) / len(t), t[len(t) // 2], t[0], ok
+
+        cpu_m = 1 << 18
+        ha = dict(slab=c2[:cpu_m * 64], stride=64)
+        r, t = timed(lambda: pktgpu.compare(ha, ha), args.cpu_budget)
+        cpu = {"value": round(r * cpu_m / t / 1e9, 6), "unit": "Gpkt/s", "cores": 1, "kind": "port",
+               "sample": f"{r} x {cpu_m} pairs of pkt_compare_host (the CPU model: the reference's zip/filter/count, "
+                         "packet.rs:347), 1 thread"}
+        how = {"measured": "mean over the iterations of HIP events around ONE call's two kernels (compare, summary "
+                           "copy-out), the result taken between calls; a ring of 4 (a, b) pairs",
+               "all_equal": "every pair EQUAL, matching = first_diff = 64, checked on the device"}
+        # the torch expression for the fixed-stride, same-length case, same ring, same run
+        tms = event_ms(lambda k_: (slabs[k_ % len(slabs)].view(n, 64) == copies[k_ % len(slabs)].view(n, 64)).sum(1), it)
+        # the ignores at work: copies whose 6 bytes of the 4 ignored fields differ in every packet (a device
+        # under test that rewrites them), still EQUAL under the ignores; masks are built only for chunks
+        # that hold a difference, so the identical copies above do not pay for them
+        rewritten = [c_.clone() for c_ in copies]
+        for c_ in rewritten:
+            c_.view(n, 64)[:, [15, 18, 19, 22, 24, 25]] ^= 0x55
+        shapes = (("c2", [(c_, None, 64, None, None) for c_ in copies], 0, (("", []), ("_ign4", ign4))),
+                  ("pcap", [(c_[0], None, None, c_[2], c_[3]) for c_ in caps], 8 + 4, (("", []), ("_ign4", ign4))),
+                  ("c2_rewritten", [(c_, None, 64, None, None) for c_ in rewritten], 0, (("_ign4", ign4),)))
+        for tag, bs, idx_b, runs in shapes:
+            for sfx, ignore in runs:
+                ms, med, best, ok = compare_ms(bs, ignore)
+                extra = dict(how, parity_all_equal=ok, median_us=round(med * 1e3, 2), min_us=round(best * 1e3, 2),
+                             ignores=len(ignore))
+                if tag == "c2":
+                    extra["torch_baseline"] = {"expr": "(A.view(n, 64) == B.view(n, 64)).sum(1)", "us": round(tms * 1e3, 2),
+                                               "kernel_speedup_vs_torch": round(tms / ms, 3)}
+                # read: la + lb, b's offsets / lens when indexed, with ignores n_hdrs and 3 slots of the chain;
+                # written: result, matching, first_diff
+                line(f"compare_{tag}{sfx}", n, ms, 128 + idx_b + (1 + 3 * 3 if ignore else 0), 9, cpu, extra)
+        del caps, copies, rewritten
     if want("extract_c2"):
         from pktgpu import fields as F
         specs = [(h, 0, s0, e0) for h in ("Ether", "IPv4", "UDP") for (s0, e0) in F.FIELDS[schema.HDR_ID[h]].values()]
