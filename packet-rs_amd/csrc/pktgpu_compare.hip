@@ -355,11 +355,7 @@ int cmp_queue(pkt_ctx_t* ctx, const pkt_batch_t* a, const pkt_batch_t* b, const 
         return fail(ctx, PKT_ERR_INVALID_ARG, "a queued compare's result has not been taken on this ctx (pkt_compare_result)");
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
-    if (!c.ctl) {
-        e = hipHostMalloc(reinterpret_cast<void**>(&c.ctl), 64, hipHostMallocMapped);
-        if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&c.ctl_dev), c.ctl, 0);
-        if (e != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (compare)");
-    }
+    if ((e = c.ensure(64)) != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (compare)");
     if (!c.acc) {
         const size_t bytes = (size_t)kCmpSlots * kCmpSlotWords * sizeof(uint64_t);
         if ((e = hipMalloc(reinterpret_cast<void**>(&c.acc), bytes)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (compare)");
@@ -430,8 +426,7 @@ int pkt_compare_batch_async(pkt_ctx_t* ctx, const pkt_batch_t* a, const pkt_batc
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc = cmp_queue(ctx, a, b, chain_a, ignore, nignore, result, matching, first_diff, s);
     if (rc != PKT_SUCCESS) return rc;
-    ctx->cmp.pending = true;
-    ctx->cmp.pending_stream = s;
+    ctx->cmp.mark(s);
     return PKT_SUCCESS;
 }
 
@@ -440,9 +435,7 @@ int pkt_compare_result(pkt_ctx_t* ctx, pkt_cmp_summary_t* summary) {
     if (!ctx) return PKT_ERR_INVALID_ARG;
     CompareScratch& c = ctx->cmp;
     if (!c.pending) return fail(ctx, PKT_ERR_INVALID_ARG, "no compare queued on this ctx");
-    const hipError_t e = hipStreamSynchronize(c.pending_stream);
-    c.pending = false;
-    c.pending_stream = nullptr;
+    const hipError_t e = c.take();
     if (e != hipSuccess) return hip_fail(ctx, e, "pkt_compare_result");
     cmp_finish(ctx, summary);
     return PKT_SUCCESS;

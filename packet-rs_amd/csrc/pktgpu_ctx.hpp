@@ -1,5 +1,7 @@
-// pktgpu_ctx.hpp — the pkt_ctx behind the C ABI's opaque handle, shared by the kernel sources
-// (pktgpu.hip: parse / extract / rewrite; pktgpu_pcap.hip: the device pcap indexer).
+// pktgpu_ctx.hpp — the pkt_ctx behind the C ABI's opaque handle and the internal entry points the sources
+// share: the kernel sources (pktgpu.hip: parse; pktgpu_rewrite.hip: getters, to_vec, setters; pktgpu_pcap.hip /
+// pktgpu_pcapw.hip: pcap indexer / writer; pktgpu_compare.hip, pktgpu_gen.hip, pktgpu_gather.hip) and the
+// host-only ones (pktgpu_ctx.cpp: lifecycle and knobs; pktgpu_hostpath.cpp: host-memory paths; pktgpu_mgpu.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,7 +27,7 @@ struct HostPipe {
     uint32_t* ilens = nullptr;
     uint64_t file_cap = 0, idx_cap = 0;  // bytes; records
     // a capture indexed and parsed as its bytes arrive (pkt_parse_pcap_host's pieces, pkt_pcap_stream_*,
-    // pktgpu.hip Ingest): a ring of kRing steps' carry words (the prefix's first uncounted record start,
+    // pktgpu_hostpath.cpp Ingest): a ring of kRing steps' carry words (the prefix's first uncounted record start,
     // its record count, the magic check) and n_hdrs maxima, and the events ordering the steps' streams
     static constexpr int kRing = 4;
     uint64_t* pcarry = nullptr;  // [kRing][4]
@@ -38,47 +40,59 @@ struct HostPipe {
     uint64_t dcol_cap = 0;       // bytes
 };
 
-// Per-region state of the device pcap indexer (pkt_pcap_index_device), grown on demand.
-struct PcapScratch {
+// A result a call queues on a stream and a later call takes: pinned host words the kernels write through their
+// device alias, and the one call in flight per ctx that has not been taken (the caller refuses another while `pending`).
+struct QueuedResult {
+    uint64_t* ctl = nullptr;      // pinned host words
+    uint64_t* ctl_dev = nullptr;  // the same words as the device addresses them
+    bool pending = false;
+    hipStream_t pending_stream = nullptr;
+    hipError_t ensure(size_t bytes) {  // the pinned words, allocated once
+        if (ctl) return hipSuccess;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ctl), bytes, hipHostMallocMapped);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctl_dev), ctl, 0);
+        return e;
+    }
+    void mark(hipStream_t s) {  // queued on s, not yet taken
+        pending = true;
+        pending_stream = s;
+    }
+    hipError_t take() {  // wait for the queued call; the words are the caller's to read and reuse
+        const hipError_t e = hipStreamSynchronize(pending_stream);
+        pending = false;
+        pending_stream = nullptr;
+        return e;
+    }
+};
+
+// Per-region state of the device pcap indexer (pkt_pcap_index_device), grown on demand.  Its result words:
+// magic, total, error; pending: a capture queued by pkt_parse_pcap_async / pkt_parse_pcap_host_async.
+struct PcapScratch : QueuedResult {
     void* buf = nullptr;   // the ticket, nb_cap scan-block states, then k_cap regions' words
     uint64_t bytes = 0;
     uint32_t k_cap = 0;    // regions the buffer holds (its layout is fixed by k_cap / nb_cap)
     uint32_t nb_cap = 0;   // scan-block states the buffer holds
-    uint64_t* ctl = nullptr;      // pinned host words the indexer reads back (magic, total, error)
-    uint64_t* ctl_dev = nullptr;  // the same words as the device addresses them (the kernel writes them)
     uint32_t epoch = 0;           // per call: block states of older calls are ignored, not cleared
     uint32_t scan_resident = 0;   // scan-kernel blocks resident at once (0 = not yet queried)
     bool scan64 = false;          // pkt_ctx_set_pcap_scan64: 64-bit scan compositions for every file
-    // a capture queued by pkt_parse_pcap_async / pkt_parse_pcap_host_async whose outcome (the words
-    // above) has not been taken yet: no other index call may reuse the scratch until it is
-    bool pending = false;
-    hipStream_t pending_stream = nullptr;
 };
 
 // Scratch of pkt_pcap_write (pktgpu_pcapw.hip), grown on demand: the totals' device words, the tile
-// sums, the window table and the record-table columns the caller did not ask for.
-struct PcapWriteScratch {
+// sums, the window table and the record-table columns the caller did not ask for.  Its result words:
+// [total bytes, records]; pending: a write queued by pkt_pcap_write_async.
+struct PcapWriteScratch : QueuedResult {
     void* buf = nullptr;
     uint64_t bytes = 0;
-    uint64_t* ctl = nullptr;      // pinned host words: [total bytes, records]
-    uint64_t* ctl_dev = nullptr;  // the same words as the device addresses them
     uint64_t dst_len = 0;         // the last queued write's capacity (total > dst_len = it did not fit)
-    // a write queued by pkt_pcap_write_async whose result has not been taken: one in flight per ctx
-    bool pending = false;
-    hipStream_t pending_stream = nullptr;
 };
 
 // Scratch of pkt_compare_batch (pktgpu_compare.hip): 256 slots of four device words the blocks add
 // their counts to (equal, len, bytes; the lowest bad index as the maximum of its complement), all zero
-// between calls, and the pinned words their sums are copied to.
-struct CompareScratch {
+// between calls, and the pinned words their sums are copied to: [n_equal, n_len, n_bytes, first_bad
+// (~0: none)]; pending: a compare queued by pkt_compare_batch_async.
+struct CompareScratch : QueuedResult {
     uint64_t* acc = nullptr;      // device: the slots
-    uint64_t* ctl = nullptr;      // pinned host words: [n_equal, n_len, n_bytes, first_bad (~0: none)]
-    uint64_t* ctl_dev = nullptr;  // the same words as the device addresses them
     uint64_t n = 0;               // the last queued compare's n (first_bad when every pair is equal)
-    // a compare queued by pkt_compare_batch_async whose result has not been taken: one in flight per ctx
-    bool pending = false;
-    hipStream_t pending_stream = nullptr;
 };
 
 // Element size of each pkt_out_t column, in declaration order (slot columns: one slot; the
@@ -115,16 +129,16 @@ struct MaxScratch {
 };
 
 struct pkt_ctx {
-    int device;
+    int device = 0;
     HostPipe hp;
     PcapScratch pc;
     PcapWriteScratch pw;
     CompareScratch cmp;
     MaxScratch mx;
-    uint32_t window;  // 0 = auto
-    int fast;         // register fast path for Ether/IPv4/UDP|TCP packets
-    int staging;      // 0 = auto, 1 = per-lane windows, 2 = wave span (LDS-DMA)
-    int walk;         // 0 = auto, 1 = waterfall, 2 = lockstep
+    uint32_t window = 0;  // 0 = auto
+    int fast = 1;         // register fast path for Ether/IPv4/UDP|TCP packets
+    int staging = 0;      // 0 = auto, 1 = per-lane windows, 2 = wave span (LDS-DMA)
+    int walk = 0;         // 0 = auto, 1 = waterfall, 2 = lockstep
     uint64_t host_piece = 0;  // pkt_parse_pcap_host: bytes of file per copied piece (0 = kHostPiece)
     // pkt_to_vec_batch: device words, nonzero = a chunk holds bytes of two records; a ring, one word
     // per call, so calls in flight on several streams do not share one; a word is reused only after
@@ -154,6 +168,24 @@ inline int hip_fail(pkt_ctx* ctx, hipError_t e, const char* what) {
     return PKT_ERR_HIP;
 }
 
+// The parse every entry point ends in (pktgpu.hip): pkt_parse_batch's validation and launch, with the extras the
+// internal callers need.  It does NOT refuse slab_len < 16 (the public entries, pktgpu_parse_counted and
+// pktgpu_parse_rows_async do): the host pipeline parses 1-byte views of buffers that have 16 readable bytes.
+struct ParseOpts {
+    uint64_t off_bias = 0;             // subtracted from every offsets[i]: b->slab starts at that byte of the batch's
+    int staging = 0;                   // 0 = the ctx's knob (pkt_ctx_set_staging), else that mode
+    uint32_t* nh_max = nullptr;        // non-NULL: MaxScratch::kSpread words the kernel reduces the largest n_hdrs into
+    uint64_t slot_stride = 0;          // the slot columns' row stride (0 = b->n)
+    const uint64_t* n_dev = nullptr;   // the record count taken on the device (blocks past it exit); one launch
+    const uint64_t* i0_dev = nullptr;  // with n_dev: the launch parses [*i0_dev (NULL: 0), min(b->n, *n_dev)) ...
+    uint64_t grid_n = 0;               // ... with a grid for grid_n packets, the most that range can hold (0 = b->n)
+};
+int pktgpu_parse(pkt_ctx_t* ctx, const pkt_batch_t* b, int entry, const pkt_out_t* out, void* stream,
+                 const ParseOpts& opts = {});
+
+// The ctx's MaxScratch words, allocated once (pktgpu.hip).
+hipError_t pktgpu_ensure_max_scratch(pkt_ctx_t* ctx);
+
 // pkt_parse_batch that also leaves the batch's largest n_hdrs (its used slot rows, <= PKT_MAX_HDRS
 // for a parsed packet) in pinned host memory: *rows_host is valid once `stream` has passed the call.
 // The reduction is fused into the parse kernel.  Used by the multi-GPU gather (pktgpu_mgpu.cpp).
@@ -169,7 +201,7 @@ int pktgpu_parse_counted(pkt_ctx_t* ctx, const pkt_batch_t* b, int entry, const 
 
 // The device pcap indexer's kernels queued on `stream` (no host wait; *count_dev = the device word
 // holding the record count, 0 after an error), and its outcome once the stream has passed them
-// (pktgpu_pcap.hip).  Used by pkt_parse_pcap_host_async (pktgpu.hip).
+// (pktgpu_pcap.hip).  Used by the piecewise capture ingest (pktgpu_hostpath.cpp).
 // partial / count_out: index buf[0, len) as the PREFIX of a capture still arriving (a record running past
 // its end ends the index, no error) and write the record count to the device word count_out (NULL: the
 // ctx's own word, returned in *count_dev either way).  pktgpu_pcap_reserve: scratch for a file of len bytes.

@@ -89,7 +89,7 @@ hipError_t pktgpu_repack_launch(const RepackPiece* tab_dev, uint32_t np, uint32_
     return hipGetLastError();
 }
 
-// ---- the capture-in-host-memory path's column export (pkt_parse_pcap_host, pktgpu.hip) ----
+// ---- the capture-in-host-memory path's column export (pkt_parse_pcap_host, pktgpu_hostpath.cpp) ----
 // A piece's records [lo, hi) (device words: the prefix counts) were parsed into DEVICE columns laid out
 // like the caller's host columns (same element size, slot rows strided by cap); this kernel copies each
 // column's range [lo, hi) — each slot row's below the piece's largest n_hdrs — into the caller's pinned

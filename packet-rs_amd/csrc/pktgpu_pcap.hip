@@ -1250,11 +1250,7 @@ static int pcap_launch(pkt_ctx_t* ctx, const uint8_t* buf, uint64_t len, uint64_
     // (file positions and prefixes a look-back could take for a state published in this epoch).
     PcapScratch& pc = ctx->pc;
     if ((e = pcap_reserve(ctx, K, s)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pcap index)");
-    if (!pc.ctl) {
-        e = hipHostMalloc(reinterpret_cast<void**>(&pc.ctl), 8 * kHostWords, hipHostMallocMapped);
-        if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&pc.ctl_dev), pc.ctl, 0);
-        if (e != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (pcap index)");
-    }
+    if ((e = pc.ensure(8 * kHostWords)) != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (pcap index)");
     // a new epoch per call (block states of older calls are ignored, not cleared; the block-state
     // area only ever holds epoch-tagged states, reset in full on wrap)
     if (++pc.epoch >= (1u << kEpochBits)) {
@@ -1348,9 +1344,7 @@ int pktgpu_pcap_finish(pkt_ctx_t* ctx, uint64_t* n_out) { return pcap_finish(ctx
 int pktgpu_pcap_take(pkt_ctx_t* ctx, uint64_t* n_out) {
     PcapScratch& pc = ctx->pc;
     if (!pc.pending) return fail(ctx, PKT_ERR_INVALID_ARG, "no capture queued on this ctx");
-    const hipError_t e = hipStreamSynchronize(pc.pending_stream);
-    pc.pending = false;
-    pc.pending_stream = nullptr;
+    const hipError_t e = pc.take();
     if (e != hipSuccess) return hip_fail(ctx, e, "pkt_parse_pcap_result");
     return pcap_finish(ctx, n_out);
 }
@@ -1428,8 +1422,7 @@ int pkt_parse_pcap_async(pkt_ctx_t* ctx, const uint8_t* buf, uint64_t len, int e
         (void)hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream));  // nothing left in flight
         return rc;
     }
-    ctx->pc.pending = true;
-    ctx->pc.pending_stream = reinterpret_cast<hipStream_t>(stream);
+    ctx->pc.mark(reinterpret_cast<hipStream_t>(stream));
     return PKT_SUCCESS;
 }
 

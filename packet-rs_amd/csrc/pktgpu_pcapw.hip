@@ -412,11 +412,7 @@ int pw_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const uint8_t* select, uint32
         if ((e = hipMalloc(&pw.buf, need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pcap write)");
         pw.bytes = need;
     }
-    if (!pw.ctl) {
-        e = hipHostMalloc(reinterpret_cast<void**>(&pw.ctl), 64, hipHostMallocMapped);
-        if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&pw.ctl_dev), pw.ctl, 0);
-        if (e != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (pcap write)");
-    }
+    if ((e = pw.ensure(64)) != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (pcap write)");
     char* p = static_cast<char*>(pw.buf);
     uint64_t* tot = reinterpret_cast<uint64_t*>(p);
     uint64_t* blk_bytes = reinterpret_cast<uint64_t*>(p + o_bytes);
@@ -486,8 +482,7 @@ int pkt_pcap_write_async(pkt_ctx_t* ctx, const pkt_batch_t* batch, const uint8_t
     const int rc = pw_queue(ctx, batch, select, snaplen, tv_sec, tv_usec, ts_sec, ts_usec, dst, dst_len, rec_offsets,
                             rec_lens, src_index, s);
     if (rc != PKT_SUCCESS) return rc;
-    ctx->pw.pending = true;
-    ctx->pw.pending_stream = s;
+    ctx->pw.mark(s);
     return PKT_SUCCESS;
 }
 
@@ -497,9 +492,7 @@ int pkt_pcap_write_result(pkt_ctx_t* ctx, uint64_t* bytes_out, uint64_t* n_out) 
     if (!ctx) return PKT_ERR_INVALID_ARG;
     PcapWriteScratch& pw = ctx->pw;
     if (!pw.pending) return fail(ctx, PKT_ERR_INVALID_ARG, "no write queued on this ctx");
-    const hipError_t e = hipStreamSynchronize(pw.pending_stream);
-    pw.pending = false;
-    pw.pending_stream = nullptr;
+    const hipError_t e = pw.take();
     if (e != hipSuccess) return hip_fail(ctx, e, "pkt_pcap_write_result");
     return pw_finish(ctx, bytes_out, n_out);
 }

@@ -130,6 +130,8 @@ __global__ __launch_bounds__(256) void ceiling_groups_kernel(const uint8_t* slab
     }
 }
 
+constexpr int kNumCols = sizeof(pkt_out_t) / sizeof(void*);  // pkt_out_t: one pointer per column
+
 }  // namespace
 
 extern "C" int pkt_probe_ceiling_groups(const uint8_t* slab, uint64_t n, uint32_t stride, uint32_t slots,
@@ -138,7 +140,7 @@ extern "C" int pkt_probe_ceiling_groups(const uint8_t* slab, uint64_t n, uint32_
     if (!slab || !out || n == 0 || n >= (1ull << 26) || stride < 64 || (stride & 15) || slots > PKT_MAX_HDRS)
         return PKT_ERR_INVALID_ARG;
     const void* const* cols = reinterpret_cast<const void* const*>(out);
-    static const int lo[7] = {0, 7, 10, 14, 27, 35, 45}, hi[7] = {7, 10, 14, 27, 35, 45, 49};
+    static const int lo[7] = {0, 7, 10, 14, 27, 35, 45}, hi[7] = {7, 10, 14, 27, 35, 45, kNumCols};
     for (int g = 0; g < 7; g++) {
         if (g == 4 && cols[lo[g]]) return PKT_ERR_INVALID_ARG;  // IPv6: not part of any probe shape
         if (g > 0 && !cols[lo[g]]) continue;
@@ -156,7 +158,7 @@ extern "C" int pkt_probe_ceiling(const uint8_t* slab, uint64_t n, uint32_t strid
     if (!slab || !out || n == 0 || n >= (1ull << 26) || stride < 64 || (stride & 15)) return PKT_ERR_INVALID_ARG;
     // pkt_out_t members 0-9 (chain, Ether), 14-26 (IPv4) and 45-48 (UDP)
     const void* const* cols = reinterpret_cast<const void* const*>(out);
-    for (int c = 0; c < 49; c++) {
+    for (int c = 0; c < kNumCols; c++) {
         const bool need = c < 10 || (c >= 14 && c < 27) || c >= 45;
         if (need && !cols[c]) return PKT_ERR_INVALID_ARG;
     }
