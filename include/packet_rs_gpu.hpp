@@ -241,6 +241,22 @@ class Parser {
         return sm;
     }
 
+    // Packet::push / insert / pop / remove (packet.rs:117-164) then to_vec (385-392) over a parsed device
+    // batch (pkt_edit_batch): the program `ops` (at most 8; an INSERT's bytes are hdr_data[data_off ..],
+    // host memory captured at the call) applied to every packet's header list — or only where select[i] !=
+    // 0 — and the result written to its slot of `dst` (dst + dst_offsets[i], or i * slot; at most `slot`
+    // bytes).  out_len / edit_status (PKT_EDIT_*): device arrays of n, each may be NULL; out_chain: the
+    // edited packets' own chain columns, for the calls that follow.  Asynchronous on `s`.
+    void edit(const pkt_batch_t& b, const pkt_out_t& parsed, const std::vector<pkt_edit_op_t>& ops,
+              const std::vector<uint8_t>& hdr_data, uint8_t* dst, uint64_t dst_len, uint32_t slot,
+              const uint64_t* dst_offsets = nullptr, const uint8_t* select = nullptr, uint32_t* out_len = nullptr,
+              uint8_t* edit_status = nullptr, const pkt_out_t* out_chain = nullptr, hipStream_t s = nullptr) {
+        check(pkt_edit_batch(ctx_, &b, &parsed, ops.data(), (uint32_t)ops.size(), hdr_data.data(),
+                             (uint32_t)hdr_data.size(), select, dst, dst_len, dst_offsets, slot, out_len, edit_status,
+                             out_chain, s),
+              ctx_, "pkt_edit_batch");
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

@@ -595,6 +595,91 @@ int pkt_compare_host(const pkt_batch_t *a, const pkt_batch_t *b, const pkt_chain
                      const pkt_field_spec_t *ignore, uint32_t nignore, uint8_t *result, uint32_t *matching,
                      uint32_t *first_diff, pkt_cmp_summary_t *summary);
 
+/* ---- editing a batch's header lists ----
+ * Packet::push / insert / pop / remove (packet.rs:117-164), `Add` (75-84) and the to_vec that
+ * serialises the result (385-392) as a batch operation.  For packet i of a parsed batch the
+ * reference's Packet is the list L whose entry j is the packet's bytes [hdr_off[j], hdr_off[j] +
+ * pkt_hdr_size(hdr_type[j])), in list order (Q2 order for GRE options), with the payload
+ * [payload_off, payload_off + payload_len).  The `nops` <= 8 ops of the program, the same for every
+ * packet, are applied to L in order; then to_vec is written: the list's slices back to back, then
+ * the payload.
+ *  - PKT_EDIT_POP         Packet::pop: drops the last entry; no-op on an empty list (143-147).
+ *  - PKT_EDIT_REMOVE_AT   Packet::remove(index): no-op when index >= len (160-164).
+ *  - PKT_EDIT_REMOVE_HDR  (extension) removes the `index`-th entry of `hdr_type` in the CURRENT list,
+ *                         counted as Index<&str> counts (64-66); no-op when the list has none.
+ *  - PKT_EDIT_INSERT      a new header of hdr_type whose pkt_hdr_size(hdr_type) bytes are
+ *                         hdr_data[data_off ..]: index 0 = Packet::insert (129-131), index PKT_EDIT_END
+ *                         = Packet::push (117-119; `Add` is push header by header), any other index =
+ *                         Vec::insert(min(index, len)) (extension).
+ *  - batch / parsed: as pkt_to_vec_batch: `parsed` holds the chain columns of a parse of the same batch
+ *    (status, n_hdrs, hdr_type, hdr_off, payload_off, payload_len are required and read; hdr_mask and the
+ *    field columns are ignored).  n_hdrs is taken as min(n_hdrs, PKT_MAX_HDRS) and every slice is clamped
+ *    to the packet's [0, len) under the pkt_batch_t rules: whatever the columns hold, no byte outside
+ *    the packet is read and none outside its slot is written (columns that are not a parse of the batch
+ *    give unspecified output bytes, never other accesses).
+ *  - hdr_data: HOST memory, hdr_data_len <= 320 bytes, captured at the call (the caller may free it on
+ *    return).  Every INSERT names pkt_hdr_size(hdr_type) bytes inside it, hdr_type in 1..21.
+ *  - select: device [n] or NULL; a packet with select[i] == 0 is written with no op applied (plain
+ *    to_vec) and still counts as PKT_EDIT_OK.
+ *  - dst: device, 16-byte aligned, dst_len bytes.  Packet i owns [o_i, o_i + room_i), o_i = dst_offsets ?
+ *    dst_offsets[i] : i * slot (any alignment), room_i = min(slot, dst_len - o_i), 0 when o_i >= dst_len.
+ *    The caller keeps the slots disjoint from each other and from the source slab.  Exactly the bytes
+ *    [o_i, o_i + out_len[i]) are written, each once; no other byte of dst is written, not even with
+ *    its own value, and dst is never read (a packet's first and last partial 16-byte chunks go out in
+ *    narrower stores, not as a read-merge-write).
+ *  - edit_status[i] (device [n], may be NULL): PKT_EDIT_OK = written; PKT_EDIT_SKIPPED = the source
+ *    status is not PKT_OK (the reference panicked: there is no Packet); PKT_EDIT_DEPTH = the list
+ *    exceeded PKT_MAX_HDRS right after some INSERT (even if a later op would shrink it);
+ *    PKT_EDIT_NO_ROOM = the new length exceeds room_i or 65535.  For the three others nothing is
+ *    written and out_len[i] = 0.  out_len (device [n]) may be NULL.
+ *  - out_chain (may be NULL): a pkt_out_t of which only the seven chain columns are honoured, each of
+ *    which may be NULL.  It receives the edited Packet's own list, not a re-parse of its bytes: n_hdrs,
+ *    slot-major hdr_type / hdr_off for slots < n_hdrs (entry k's offset = the sum of the sizes before
+ *    it; later slots are not written, as pkt_parse_batch leaves them), payload_off, payload_len,
+ *    hdr_mask, and status = PKT_OK.  For the other results status = the source status (SKIPPED),
+ *    PKT_DEPTH_LIMIT (DEPTH) or PKT_TRUNCATED (NO_ROOM) and n_hdrs = payload_off = payload_len = hdr_mask
+ *    = 0: pkt_parse_batch's contract for a failed packet.  So {dst, o_i, out_len} with out_chain feeds
+ *    pkt_set_fields_csum, pkt_extract_fields, pkt_compare_batch's ignores, pkt_pcap_write and
+ *    pkt_to_vec_batch with no second parse.
+ *  - The per-packet encap flow: INSERT the constant outer headers (e.g. Vxlan, UDP, IPv4, Ether, each at
+ *    index 0), then pkt_set_fields_csum on {dst, out_len} with out_chain: IPv4 total_len = out_len - 14
+ *    and UDP length = out_len - 34 as per-packet values, ipv4_occurrence = 0 for the checksum.
+ *  - PKT_ERR_INVALID_ARG, before any launch: nops > 8, an unknown kind, an INSERT with a bad type or
+ *    bytes running past hdr_data_len, hdr_data_len > 320, a NULL required pointer, n >= 2^32, slot == 0.
+ *    n == 0 succeeds and does nothing.
+ * Asynchronous on `stream`, like pkt_to_vec_batch: no host wait and no summary.  pkt_edit_host is the
+ * same operation on HOST pointers (batch, parsed, select, dst and the outputs) and needs no device or
+ * ctx. */
+#define PKT_EDIT_END 0xFF
+typedef enum pkt_edit_kind {
+    PKT_EDIT_POP        = 0,
+    PKT_EDIT_REMOVE_AT  = 1,
+    PKT_EDIT_REMOVE_HDR = 2,
+    PKT_EDIT_INSERT     = 3
+} pkt_edit_kind_t;
+typedef enum pkt_edit_status {
+    PKT_EDIT_OK      = 0,
+    PKT_EDIT_SKIPPED = 1,
+    PKT_EDIT_DEPTH   = 2,
+    PKT_EDIT_NO_ROOM = 3
+} pkt_edit_status_t;
+typedef struct pkt_edit_op {
+    uint8_t  kind;      /* pkt_edit_kind_t */
+    uint8_t  hdr_type;  /* REMOVE_HDR, INSERT */
+    uint8_t  index;     /* REMOVE_AT: position; REMOVE_HDR: occurrence; INSERT: position or PKT_EDIT_END */
+    uint8_t  reserved;
+    uint32_t data_off;  /* INSERT: the header's first byte in hdr_data */
+} pkt_edit_op_t;
+size_t pkt_sizeof_edit_op(void);
+int pkt_edit_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_out_t *parsed, const pkt_edit_op_t *ops,
+                   uint32_t nops, const uint8_t *hdr_data, uint32_t hdr_data_len, const uint8_t *select,
+                   uint8_t *dst, uint64_t dst_len, const uint64_t *dst_offsets, uint32_t slot,
+                   uint32_t *out_len, uint8_t *edit_status, const pkt_out_t *out_chain, void *stream);
+int pkt_edit_host(const pkt_batch_t *batch, const pkt_out_t *parsed, const pkt_edit_op_t *ops, uint32_t nops,
+                  const uint8_t *hdr_data, uint32_t hdr_data_len, const uint8_t *select, uint8_t *dst,
+                  uint64_t dst_len, const uint64_t *dst_offsets, uint32_t slot, uint32_t *out_len,
+                  uint8_t *edit_status, const pkt_out_t *out_chain);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

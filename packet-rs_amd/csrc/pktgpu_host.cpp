@@ -88,6 +88,7 @@ size_t pkt_sizeof_batch(void) { return sizeof(pkt_batch_t); }
 size_t pkt_sizeof_out(void) { return sizeof(pkt_out_t); }
 size_t pkt_sizeof_field_spec(void) { return sizeof(pkt_field_spec_t); }
 size_t pkt_sizeof_cmp_summary(void) { return sizeof(pkt_cmp_summary_t); }
+size_t pkt_sizeof_edit_op(void) { return sizeof(pkt_edit_op_t); }
 
 const char* pkt_hdr_name(int t) { return (t > 0 && t < PKT_HDR_COUNT) ? kHdrs[t].name : nullptr; }
 int pkt_hdr_size(int t) { return (t > 0 && t < PKT_HDR_COUNT) ? kHdrs[t].size : 0; }
@@ -244,6 +245,110 @@ int pkt_compare_host(const pkt_batch_t* a, const pkt_batch_t* b, const pkt_chain
         if (r != PKT_CMP_EQUAL && sum.first_bad == n) sum.first_bad = i;
     }
     if (summary) *summary = sum;
+    return PKT_SUCCESS;
+}
+
+// pkt_edit_batch on host pointers (the CPU model of pktgpu_edit.hip): Packet::push / insert / pop /
+// remove (packet.rs:117-164) on every packet's header list, then to_vec (385-392), packet by packet.
+int pkt_edit_host(const pkt_batch_t* b, const pkt_out_t* parsed, const pkt_edit_op_t* ops, uint32_t nops,
+                  const uint8_t* hdr_data, uint32_t hdr_data_len, const uint8_t* select, uint8_t* dst, uint64_t dst_len,
+                  const uint64_t* dst_offsets, uint32_t slot, uint32_t* out_len, uint8_t* edit_status,
+                  const pkt_out_t* out_chain) {
+    if (!b || !parsed || nops > 8 || (nops && !ops) || hdr_data_len > 320 || slot == 0 || b->n >= (1ull << 32))
+        return PKT_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < nops; k++) {
+        if (ops[k].kind > PKT_EDIT_INSERT) return PKT_ERR_INVALID_ARG;
+        if (ops[k].kind != PKT_EDIT_INSERT) continue;
+        if (ops[k].hdr_type == 0 || ops[k].hdr_type >= PKT_HDR_COUNT || !hdr_data ||
+            (uint64_t)ops[k].data_off + kHdrs[ops[k].hdr_type].size > hdr_data_len)
+            return PKT_ERR_INVALID_ARG;
+    }
+    const uint64_t n = b->n;
+    if (n == 0) return PKT_SUCCESS;
+    if (!dst || !parsed->status || !parsed->n_hdrs || !parsed->hdr_type || !parsed->hdr_off || !parsed->payload_off ||
+        !parsed->payload_len)
+        return PKT_ERR_INVALID_ARG;
+    if ((b->slab_len && !b->slab) || (b->offsets && !b->lens) || (!b->offsets && b->stride == 0)) return PKT_ERR_INVALID_ARG;
+    struct Ent {
+        uint8_t type, konst;  // konst: the bytes are hdr_data[at ..], else the packet's [at ..]
+        uint32_t at, size;
+    };
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t off = b->offsets ? b->offsets[i] : i * b->stride;
+        const uint64_t left = off < b->slab_len ? b->slab_len - off : 0;
+        uint64_t l = b->lens ? b->lens[i] : b->stride;
+        l = l > left ? left : l;
+        const uint32_t len = l > 65535 ? 65535u : (uint32_t)l;
+        const uint64_t o = dst_offsets ? dst_offsets[i] : i * slot;
+        const uint64_t room = o >= dst_len ? 0 : (dst_len - o < slot ? dst_len - o : slot);
+        // a slice of the packet, clamped to [0, len)
+        auto clamp = [len](uint32_t at, uint32_t size, uint32_t& a, uint32_t& s) {
+            a = at > len ? len : at;
+            s = size > len - a ? len - a : size;
+        };
+        Ent L[PKT_MAX_HDRS + 1];
+        uint32_t cnt = 0, st = parsed->status[i] == PKT_OK ? PKT_EDIT_OK : PKT_EDIT_SKIPPED;
+        uint32_t pay_at = 0, pay_len = 0;
+        if (st == PKT_EDIT_OK) {
+            uint32_t nh = parsed->n_hdrs[i];
+            nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+            for (uint32_t j = 0; j < nh; j++) {
+                Ent& e = L[cnt++];
+                e.type = parsed->hdr_type[j * n + i];
+                e.konst = 0;
+                clamp(parsed->hdr_off[j * n + i], e.type < PKT_HDR_COUNT ? kHdrs[e.type].size : 0, e.at, e.size);
+            }
+            clamp(parsed->payload_off[i], parsed->payload_len[i], pay_at, pay_len);
+            const uint32_t run = select && !select[i] ? 0 : nops;
+            for (uint32_t k = 0; k < run && st == PKT_EDIT_OK; k++) {
+                const pkt_edit_op_t& op = ops[k];
+                uint32_t at = cnt;  // the entry to remove, cnt = none
+                if (op.kind == PKT_EDIT_POP) {
+                    at = cnt ? cnt - 1 : cnt;
+                } else if (op.kind == PKT_EDIT_REMOVE_AT) {
+                    at = op.index < cnt ? op.index : cnt;
+                } else if (op.kind == PKT_EDIT_REMOVE_HDR) {
+                    uint32_t seen = 0;
+                    for (uint32_t j = 0; j < cnt && at == cnt; j++)
+                        if (L[j].type == op.hdr_type && seen++ == op.index) at = j;
+                } else {
+                    const uint32_t pos = op.index == PKT_EDIT_END || op.index > cnt ? cnt : op.index;
+                    for (uint32_t j = cnt; j > pos; j--) L[j] = L[j - 1];
+                    L[pos] = Ent{op.hdr_type, 1, op.data_off, (uint32_t)kHdrs[op.hdr_type].size};
+                    if (++cnt > PKT_MAX_HDRS) st = PKT_EDIT_DEPTH;
+                    continue;
+                }
+                if (at < cnt) {
+                    for (uint32_t j = at; j + 1 < cnt; j++) L[j] = L[j + 1];
+                    cnt--;
+                }
+            }
+        }
+        uint32_t total = pay_len;
+        for (uint32_t j = 0; j < cnt; j++) total += L[j].size;
+        if (st == PKT_EDIT_OK && (total > room || total > 65535)) st = PKT_EDIT_NO_ROOM;
+        if (st != PKT_EDIT_OK) cnt = total = pay_len = 0;
+        uint32_t pos = 0, mask = 0;
+        for (uint32_t j = 0; j < cnt; j++) {
+            if (L[j].size) memcpy(dst + o + pos, (L[j].konst ? hdr_data : b->slab + off) + L[j].at, L[j].size);
+            if (out_chain && out_chain->hdr_type) out_chain->hdr_type[j * n + i] = L[j].type;
+            if (out_chain && out_chain->hdr_off) out_chain->hdr_off[j * n + i] = (uint16_t)pos;
+            mask |= L[j].type < 32 ? 1u << L[j].type : 0u;
+            pos += L[j].size;
+        }
+        if (pay_len) memcpy(dst + o + pos, b->slab + off + pay_at, pay_len);
+        if (out_len) out_len[i] = total;
+        if (edit_status) edit_status[i] = (uint8_t)st;
+        if (out_chain) {
+            const uint8_t cs = st == PKT_EDIT_OK ? PKT_OK : st == PKT_EDIT_SKIPPED ? parsed->status[i]
+                             : st == PKT_EDIT_DEPTH ? PKT_DEPTH_LIMIT : PKT_TRUNCATED;
+            if (out_chain->status) out_chain->status[i] = cs;
+            if (out_chain->n_hdrs) out_chain->n_hdrs[i] = (uint8_t)cnt;
+            if (out_chain->payload_off) out_chain->payload_off[i] = (uint16_t)pos;
+            if (out_chain->payload_len) out_chain->payload_len[i] = (uint16_t)pay_len;
+            if (out_chain->hdr_mask) out_chain->hdr_mask[i] = mask;
+        }
+    }
     return PKT_SUCCESS;
 }
 

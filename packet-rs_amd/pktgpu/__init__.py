@@ -581,6 +581,56 @@ class Parser:
             raise RuntimeError("compare_result: no compare queued")
         return q[0] + (_cmp_summary(sm),)
 
+    def _edit_args(self, slab, parsed, ops, stride=None, n=None, offsets=None, lens=None, select=None, dst=None,
+                   dst_offsets=None, slot=None, outputs=(True, True, True)):
+        """The marshalled arguments of pkt_edit_batch (after ctx, before stream); `outputs`: whether
+        out_len, edit_status and out_chain are asked for."""
+        torch = _torch()
+        b = self._batch(slab, n, stride, offsets, lens)
+        n = b.n
+        arr, k, data = _edit_ops(self._lib, ops)
+        slot = _edit_slot(slot, stride, dst_offsets, arr, k)
+        if select is not None:
+            if select.dtype == torch.bool:
+                select = select.view(torch.uint8)
+            assert select.dtype == torch.uint8 and select.is_cuda and select.numel() == n
+        if dst is None:
+            if dst_offsets is not None:
+                raise ValueError("edit: dst_offsets needs dst")
+            dst = torch.empty(n * slot, dtype=torch.uint8, device=self.torch_device)
+        assert dst.dtype == torch.uint8 and dst.is_cuda and dst.is_contiguous()
+        if dst_offsets is not None:
+            assert dst_offsets.dtype == torch.uint64 and dst_offsets.is_cuda and dst_offsets.numel() == n
+        out_len = torch.empty(n, dtype=torch.uint32, device=self.torch_device) if outputs[0] else None
+        status = torch.empty(n, dtype=torch.uint8, device=self.torch_device) if outputs[1] else None
+        chain = None
+        if outputs[2]:
+            chain = {c: torch.zeros(schema.column_shape(c, n), dtype=_tdtype(schema.column_dtype(c)),
+                                    device=self.torch_device) for c in schema.columns_of(["chain"])}
+        po = self.out_struct(parsed)
+        oc = self.out_struct(chain) if chain is not None else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        args = (ctypes.byref(b), ctypes.byref(po), arr, k, data, len(data), ptr(select), ptr(dst), dst.numel(),
+                ptr(dst_offsets), slot, ptr(out_len), ptr(status), ctypes.byref(oc) if oc is not None else None)
+        return args, (dst, out_len, status, chain), (b, po, oc, arr, data)
+
+    def edit(self, slab, parsed, ops, stride=None, n=None, offsets=None, lens=None, select=None, dst=None,
+             dst_offsets=None, slot=None, stream=None):
+        """pkt_edit_batch: Packet::push / insert / pop / remove on every packet's header list, then
+        to_vec -> (dst, out_len uint32, status uint8, chain).  `parsed`: the chain columns of a parse of
+        the batch.  `ops` (at most 8, the same program for every packet): ("pop",), ("remove", k),
+        ("remove_hdr", hdr, occurrence), ("insert", hdr, bytes[, index]) (index 0 by default, as
+        Packet::insert) and ("push", hdr, bytes).  `select`: a uint8 / bool device tensor [n], the
+        packets with 0 are written unedited.  Packet i goes to dst + dst_offsets[i], or i * slot, and
+        may take `slot` bytes (default: stride plus the inserted bytes, rounded up to 16); dst=None
+        allocates n * slot bytes.  status: pktgpu.EDIT_OK / _SKIPPED / _DEPTH / _NO_ROOM; `chain`: the
+        edited packets' chain columns ({column: tensor}; slot rows past n_hdrs are 0), which with
+        (dst, out_len) feed set_fields, extract_fields, compare, pcap_write and to_vec with no second
+        parse.  Asynchronous on `stream`."""
+        args, out, keep = self._edit_args(slab, parsed, ops, stride, n, offsets, lens, select, dst, dst_offsets, slot)
+        self._check(self._L.pkt_edit_batch(self._ctx, *args, self._stream(stream)), "pkt_edit_batch")
+        return out
+
     def pcap_index_device_timed(self, buf, offsets, lens, stream=None):
         """pkt_pcap_index_device_timed into the caller's device `offsets` / `lens` (cap = their
         length): (record count, [guess, scan, emit] kernel ms from HIP events between them)."""
@@ -724,6 +774,94 @@ def compare(a, b, ignore=(), chain=None):
     if rc != 0:
         raise ValueError(f"pkt_compare_host failed ({rc})")
     return res, mt, fd, _cmp_summary(sm)
+
+
+EDIT_OK, EDIT_SKIPPED, EDIT_DEPTH, EDIT_NO_ROOM = 0, 1, 2, 3
+EDIT_POP, EDIT_REMOVE_AT, EDIT_REMOVE_HDR, EDIT_INSERT = 0, 1, 2, 3
+EDIT_END = 0xFF
+
+
+def _edit_ops(lib, ops):
+    """The op tuples of Parser.edit -> (PktEditOp array, count, hdr_data bytes)."""
+    k = len(ops)
+    arr = (lib.PktEditOp * max(1, k))()
+    # hdr_data in LIST order where the program shows it (an insert at index 0 goes in front of the bytes so
+    # far, any other behind them): headers that end up next to each other, as an encap's outer headers do,
+    # are then one run of hdr_data, which the kernel copies as one segment
+    pieces = []  # (op index, bytes)
+    hid = lambda t: HDR_ID[t] if isinstance(t, str) else int(t)  # noqa: E731
+    for i, op in enumerate(ops):
+        kind = op[0]
+        if kind == "pop":
+            arr[i] = lib.PktEditOp(EDIT_POP, 0, 0, 0, 0)
+        elif kind == "remove":
+            arr[i] = lib.PktEditOp(EDIT_REMOVE_AT, 0, int(op[1]), 0, 0)
+        elif kind == "remove_hdr":
+            arr[i] = lib.PktEditOp(EDIT_REMOVE_HDR, hid(op[1]), int(op[2]) if len(op) > 2 else 0, 0, 0)
+        elif kind in ("insert", "push"):
+            t = hid(op[1])
+            size = HDR_SIZES[t] if 0 < t < len(HDR_SIZES) else 0
+            raw = bytes(op[2])
+            if len(raw) < size:
+                raise ValueError(f"edit: {op[1]!r} needs {size} bytes, got {len(raw)}")
+            index = EDIT_END if kind == "push" else (int(op[3]) if len(op) > 3 else 0)
+            arr[i] = lib.PktEditOp(EDIT_INSERT, t, index, 0, 0)
+            pieces.insert(0 if index == 0 else len(pieces), (i, raw[:size]))
+        else:
+            raise ValueError(f"edit: unknown op {kind!r}")
+    data = b""
+    for i, raw in pieces:
+        arr[i].data_off = len(data)
+        data += raw
+    return arr, k, data
+
+
+def _edit_slot(slot, stride, dst_offsets, arr, k):
+    if slot is not None:
+        return int(slot)
+    if not stride:
+        raise ValueError("edit: an indexed batch needs `slot`, the room of every destination packet")
+    grow = sum(HDR_SIZES[arr[i].hdr_type] for i in range(k) if arr[i].kind == EDIT_INSERT and arr[i].hdr_type < len(HDR_SIZES))
+    return int(stride) + (grow + 15) // 16 * 16
+
+
+def edit(slab, parsed, ops, stride=None, n=None, offsets=None, lens=None, select=None, dst=None, dst_offsets=None,
+         slot=None):
+    """pkt_edit_host over numpy arrays (no device): Parser.edit's arguments with numpy arrays ->
+    (dst uint8, out_len uint32, status uint8, chain {column: array})."""
+    from . import _lib
+    L = _lib.load()
+    b, keep = _host_batch(_lib, dict(slab=slab, stride=stride, n=n, offsets=offsets, lens=lens))
+    n = b.n
+    arr, k, data = _edit_ops(_lib, ops)
+    slot = _edit_slot(slot, stride, dst_offsets, arr, k)
+    need = ("status", "n_hdrs", "hdr_type", "hdr_off", "payload_off", "payload_len")
+    cols = {c: np.ascontiguousarray(parsed[c], schema.column_dtype(c)) for c in need}
+    po = _lib.PktOut()
+    for c in need:
+        setattr(po, c, cols[c].ctypes.data if cols[c].size else None)
+    if select is not None:
+        select = np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+        assert select.size == n
+    if dst is None:
+        if dst_offsets is not None:
+            raise ValueError("edit: dst_offsets needs dst")
+        dst = np.zeros(n * slot, np.uint8)
+    assert dst.dtype == np.uint8 and dst.flags.c_contiguous
+    if dst_offsets is not None:
+        dst_offsets = np.ascontiguousarray(dst_offsets, np.uint64)
+        assert dst_offsets.size == n
+    out_len, status = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+    chain = {c: np.zeros(schema.column_shape(c, n), schema.column_dtype(c)) for c in schema.columns_of(["chain"])}
+    oc = _lib.PktOut()
+    for c, a in chain.items():
+        setattr(oc, c, a.ctypes.data if a.size else None)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    rc = L.pkt_edit_host(ctypes.byref(b), ctypes.byref(po), arr, k, data, len(data), ptr(select), ptr(dst), dst.size,
+                         ptr(dst_offsets), slot, ptr(out_len), ptr(status), ctypes.byref(oc))
+    if rc != 0:
+        raise ValueError(f"pkt_edit_host failed ({rc})")
+    return dst, out_len, status, chain
 
 
 # ----------------------------------------------------------------- PacketSlice-style host views

@@ -42,6 +42,11 @@ class PktCmpSummary(ctypes.Structure):
                 ("first_bad", ctypes.c_uint64)]
 
 
+class PktEditOp(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint8), ("hdr_type", ctypes.c_uint8), ("index", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8), ("data_off", ctypes.c_uint32)]
+
+
 class PktGatherPiece(ctypes.Structure):
     _fields_ = [("src", ctypes.c_uint64), ("dst", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
                 ("shard", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
@@ -143,6 +148,13 @@ SIGNATURES = {
     "pkt_compare_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktBatch),
                                         ctypes.POINTER(PktChain), ctypes.POINTER(PktFieldSpec), ctypes.c_uint32,
                                         _P, _P, _P, ctypes.POINTER(PktCmpSummary)]),
+    "pkt_sizeof_edit_op": (ctypes.c_size_t, []),
+    "pkt_edit_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktOut), ctypes.POINTER(PktEditOp),
+                                      ctypes.c_uint32, _P, ctypes.c_uint32, _P, _P, ctypes.c_uint64, _P, ctypes.c_uint32,
+                                      _P, _P, ctypes.POINTER(PktOut), _P]),
+    "pkt_edit_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktOut), ctypes.POINTER(PktEditOp),
+                                     ctypes.c_uint32, _P, ctypes.c_uint32, _P, _P, ctypes.c_uint64, _P, ctypes.c_uint32,
+                                     _P, _P, ctypes.POINTER(PktOut)]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -215,7 +227,8 @@ def load():
             or L.pkt_sizeof_field_spec() != ctypes.sizeof(PktFieldSpec) \
             or L.pkt_sizeof_gen_field() != ctypes.sizeof(PktGenField) \
             or L.pkt_sizeof_gather_piece() != ctypes.sizeof(PktGatherPiece) \
-            or L.pkt_sizeof_cmp_summary() != ctypes.sizeof(PktCmpSummary):
+            or L.pkt_sizeof_cmp_summary() != ctypes.sizeof(PktCmpSummary) \
+            or L.pkt_sizeof_edit_op() != ctypes.sizeof(PktEditOp):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L
     return L

@@ -18,6 +18,11 @@
                  record headers), each with no ignores and (_ign4) with 4 IPv4 fields ignored, and
                  compare_c2_rewritten_ign4, a copy that differs in those 4 fields in every packet; timed
                  per call; compare_c2 also beside the torch expression a user can write today
+  edit           pkt_edit_batch (Packet::push / insert / pop / remove, packet.rs:117-164, then to_vec), five lines:
+                 edit_identity_c2 (nops = 0 on C2, beside pkt_to_vec_batch on the same batch in the same run; and
+                 _bytes_only, with the status, length and chain outputs NULL), edit_encap_c2 (VXLAN encap, 64 ->
+                 114 bytes in 128-byte slots), edit_decap_c2 (the decap of that output through its out chain) and
+                 edit_vlan_strip_c3 (the first tag of C3 removed, 128-byte slots to 128-byte slots)
   extract_c2     every field of Ether/IPv4/UDP (19 specs, one launch) over C2 (headers.rs:195-201)
   setfields_c2   4 setters + the IPv4 checksum refresh, in place over C2 (headers.rs:315-324)
 
@@ -429,6 +434,78 @@ def main():
                 # written: result, matching, first_diff
                 line(f"compare_{tag}{sfx}", n, ms, 128 + idx_b + (1 + 3 * 3 if ignore else 0), 9, cpu, extra)
         del caps, copies, rewritten
+    if want("edit"):
+        import ctypes
+        CH = ("status", "n_hdrs", "hdr_type", "hdr_off", "payload_off", "payload_len")
+
+        def edit_line(name, srcs, parsed, ops, stride, slot, what, outputs=(True, True, True), beside=None):
+            """One pkt_edit_batch line: srcs / parsed = a ring of source slabs (fixed `stride`) and their chain
+            columns, the destinations a >= 1 GiB ring of n * slot bytes; the arguments marshalled once per
+            ring slot.  Returns the last ring slot's outputs (dst, out_len, status, chain)."""
+            ringd = max(2, (1 << 30) // (n * slot) + 1)
+            dsts = [torch.empty(n * slot, dtype=torch.uint8, device=dev) for _ in range(ringd)]
+            prep = [P._edit_args(srcs[r % len(srcs)], parsed[r % len(srcs)], ops, stride=stride, dst=dsts[r], slot=slot,
+                                 outputs=outputs) for r in range(ringd)]
+            s = P._stream(None)
+
+            def launch(k):
+                assert P._L.pkt_edit_batch(P._ctx, *prep[k % ringd][0], s) == 0
+            ms = event_ms(launch, it)
+            # parity with the host model (pkt_edit_host) on a sample, and the bytes the line moves
+            m = 1 << 14
+            dst, ln, st, ch = prep[0][1]
+            hp = {c_: np.ascontiguousarray(parsed[0][c_].cpu().numpy()[..., :m]) for c_ in CH}
+            hsrc = srcs[0][:m * stride].cpu().numpy()
+            hd, hl, hs, hc = pktgpu.edit(hsrc, hp, ops, stride=stride, slot=slot)
+            ok = np.array_equal(dst[:m * slot].cpu().numpy().reshape(m, slot)[np.arange(slot)[None, :] < hl[:, None]],
+                                hd.reshape(m, slot)[np.arange(slot)[None, :] < hl[:, None]])
+            if ln is not None:
+                ok = ok and np.array_equal(ln.cpu().numpy()[:m], hl) and np.array_equal(st.cpu().numpy()[:m], hs)
+                ok = ok and all(np.array_equal(ch[c_].cpu().numpy()[:m], hc[c_]) for c_ in ("n_hdrs", "payload_off", "hdr_mask"))
+            nh_in = float(parsed[0]["n_hdrs"].float().mean())
+            out_b = float(hl.mean())
+            nh_out = float(hc["n_hdrs"].mean())
+            src_b = float(np.minimum(hl, stride).mean()) if name != "edit_encap_c2" else 64.0
+            # read: the source bytes that reach the output + status, n_hdrs, payload_off / len and the used slot rows;
+            # written: the output bytes + (with outputs) out_len, edit_status and the seven chain columns' used rows
+            read_b = src_b + 6 + 3 * nh_in
+            write_b = out_b + ((4 + 1 + 10 + 3 * nh_out) if outputs[0] else 0)
+            r_, t_ = timed(lambda: pktgpu.edit(hsrc, hp, ops, stride=stride, slot=slot), args.cpu_budget / 2)
+            cpu = {"value": round(r_ * m / t_ / 1e9, 6), "unit": "Gpkt/s", "cores": 1, "kind": "port",
+                   "sample": f"{r_} x {m} packets of pkt_edit_host (the CPU model), 1 thread"}
+            extra = {"parity_vs_host_model": bool(ok), "what": what, "ops": len(ops), "slot": slot,
+                     "mean_out_len": round(out_b, 2), "outputs": "out_len, edit_status, out_chain" if outputs[0] else "bytes only"}
+            if beside:
+                extra["beside"] = dict(beside, edit_over_it=round(ms * 1e3 / beside["us"], 3))
+            line(name, n, ms, round(read_b, 2), round(write_b, 2), cpu, extra)
+            res = prep[ringd - 1][1]
+            del dsts, prep
+            return res
+
+        # (a) nops = 0 on C2, beside pkt_to_vec_batch on the same batch in the same run
+        tvd = [torch.empty_like(slabs[0]) for _ in range(ring2)]
+        tv_ms = event_ms(lambda k: P.to_vec(slabs[k % len(slabs)], chains[k % len(slabs)], stride=64, dst=tvd[k % ring2]), it)
+        del tvd
+        tv = {"kernel": "pkt_to_vec_batch, same slabs and chains, same run (its Python wrapper marshals per call)",
+              "us": round(tv_ms * 1e3, 2)}
+        edit_line("edit_identity_c2", slabs, chains, [], 64, 64, "nops = 0: to_vec of C2 into 64-byte slots", beside=tv)
+        edit_line("edit_identity_c2_bytes_only", slabs, chains, [], 64, 64, "the same with out_len, edit_status and out_chain NULL",
+                  outputs=(False, False, False), beside=tv)
+        # (c) VXLAN encap of C2: 64 bytes -> 114 in 128-byte slots; (d) decap of its output with its out chain
+        o50 = bytes(gen.reference_22_packets()[8].to_vec())[:50]
+        enc = [("insert", "Vxlan", o50[42:50]), ("insert", "UDP", o50[34:42]), ("insert", "IPv4", o50[14:34]),
+               ("insert", "Ether", o50[0:14])]
+        e_dst, e_len, e_st, e_ch = edit_line("edit_encap_c2", slabs, chains, enc, 64, 128,
+                                             "VXLAN encap of C2: Vxlan, UDP, IPv4, Ether inserted at index 0, 64 -> 114 bytes")
+        edit_line("edit_decap_c2", [e_dst], [e_ch], [("remove", 0)] * 4, 128, 128,
+                  "decap of edit_encap_c2's output through its out chain (no second parse): remove(0) x 4, 114 -> 64 bytes")
+        del e_dst, e_len, e_st, e_ch
+        # (b) strip the first VLAN tag of C3, 128-byte slots to 128-byte slots
+        c3 = torch.from_numpy(gen.gen_c3(n).reshape(-1)).to(dev)
+        ch3 = P.parse(c3, stride=128, columns=["chain"])
+        edit_line("edit_vlan_strip_c3", [c3], [ch3], [("remove_hdr", "Vlan", 0)], 128, 128,
+                  "remove_hdr Vlan 0 on C3 (0-2 tags, a third each): untagged packets copied whole")
+        del c3, ch3
     if want("extract_c2"):
         from pktgpu import fields as F
         specs = [(h, 0, s0, e0) for h in ("Ether", "IPv4", "UDP") for (s0, e0) in F.FIELDS[schema.HDR_ID[h]].values()]
