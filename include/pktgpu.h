@@ -755,29 +755,70 @@ int pkt_gather_plan(uint64_t col_mask, int nshards, const uint64_t *n, const uin
  * indexes and parses the records they complete while later bytes are still in flight.  Each step
  * indexes only the new bytes: the device keeps the first record start a step could not count yet (a
  * record running past the bytes so far) and the record count, and the next step starts the device
- * indexer from them (no re-walk from offset 24: the whole capture is indexed once however many steps).
- * The records, counts and errors are pkt_pcap_index's over the whole capture.
- * open: a stream on `device` (its own ctx; pkt_pcap_stream_ctx gives it for the tuning knobs) for a
- * capture of at most max_bytes (one device buffer) and `cap` records (<= 2^26; more are counted, not
- * parsed); `out` = the requested columns for cap records (slot columns strided by cap), either all
- * device memory of `device` (the parse writes them) or all pinned host memory from pkt_host_alloc (each
- * step's columns are exported over the link while the next bytes copy in); step_bytes = new bytes that
- * start a step at a push (0 = 4 MiB).
+ * indexer from them (no re-walk from offset 24: the window is indexed once however many steps).
+ *
+ * THE WINDOW.  The stream holds a WINDOW of the capture in one device buffer of max_bytes: the 24-byte
+ * global header, then the capture's bytes from the first unreleased record header onward.  Window
+ * offset w is capture offset w + released_bytes, window record i is capture record i +
+ * released_records (pkt_pcap_stream_released gives both totals); before any release the window is the
+ * capture.  Every count, offset, len and column the calls below report is the window's, as if its bytes
+ * were a capture of their own: the records, counts and errors are pkt_pcap_index's over the window.  A
+ * consumer that releases the records it is done with runs an unbounded capture in O(max_bytes) device
+ * memory: push -> poll -> use the columns and the packets (pkt_pcap_stream_batch) -> release.  A stream
+ * that never releases is one capture of at most max_bytes held whole.
+ * open: a stream on `device` (its own ctx; pkt_pcap_stream_ctx gives it for the tuning knobs) with a
+ * window of at most max_bytes (one device buffer) and `cap` records (<= 2^26; more are counted, not
+ * parsed, until a release brings them below cap); `out` = the requested columns for cap records (slot
+ * columns strided by cap), either all device memory of `device` (the parse writes them) or all pinned
+ * host memory from pkt_host_alloc (each step's columns are exported over the link while the next bytes
+ * copy in); step_bytes = new bytes that start a step at a push (0 = 4 MiB).
  * push: append n bytes (host memory; the caller may reuse it when push returns).  Pushes under 1 MiB
  * are gathered in a pinned staging ring of the stream and copied in 1 MiB pieces (or earlier, when a
- * step is due), without a wait per push; larger ones are copied from `bytes` and waited for.
- * poll: a step over the bytes not yet indexed, then wait: *n_records = the records wholly inside the
- * bytes so far (a record running past them is not an error yet), their columns written; offsets / lens
- * (HOST, [cap], may be NULL) receive their (data offset, incl_len).
+ * step is due), without a wait per push; larger ones are copied from `bytes` and waited for.  A push of
+ * more than pkt_pcap_stream_room bytes is refused (PKT_ERR_INVALID_ARG, nothing changes, the stream
+ * goes on working).
+ * room: *bytes = what a push can take now: max_bytes minus the window's bytes, staged ones included.
+ * A record whose 16 + incl_len exceeds max_bytes - 24 can never complete inside the window: sizing
+ * max_bytes above the largest record is the caller's business, and the stream does not detect it.
+ * poll: a step over the bytes not yet indexed, then wait: *n_records = the window's records wholly inside
+ * the bytes so far (a record running past them is not an error yet), their columns written; offsets /
+ * lens (HOST, [cap], may be NULL) receive their (data offset in the window, incl_len).
  * finish: the capture is complete: a last step, the tail taken as pkt_pcap_index takes it (a record
  * running past the end = PKT_ERR_INVALID_ARG; a partial record header is ignored), then as poll.
- * Errors name the call in pkt_pcap_stream_last_error; after one, every later call returns it. */
+ * release: the consumer is done with window records [0, n_records).  n_records <= min(c, cap), c = the
+ * count the last poll returned (0 when there was none since open or since the last release that cut
+ * anything); more, or any release after finish, is PKT_ERR_INVALID_ARG: nothing changes and the error
+ * is not sticky.  n_records = 0 changes nothing and succeeds.  Otherwise the window is cut at p =
+ * (offset + len) of window record n_records - 1 — the first uncounted record start when n_records = c,
+ * the header of the first record counted but not parsed when n_records = cap < c: the new window is the
+ * global header, then the old window's bytes [p, end); released_records += n_records, released_bytes +=
+ * p - 24 (the capture's bytes, not the repeated global header); the index and the
+ * columns restart at window record 0 and the next poll / finish reports the new window, records that
+ * were past cap included (open with cap = B, poll, consume, release(B): cap is a batch size).  The
+ * caller's column arrays are rewritten from index 0 and every pointer taken from pkt_pcap_stream_batch
+ * is stale, as data, after a release: consume first, then release.  Blocking: it waits for the stream's
+ * queued copies, steps and exports, moves the kept bytes down and leaves them to be indexed and parsed
+ * again by the next step, so its cost grows with the bytes KEPT (one partial record when everything
+ * polled is released), not with the bytes released.
+ * batch: *batch = the window as of the last poll / finish, an indexed DEVICE batch: slab = the stream's
+ * buffer, slab_len = the bytes that poll had indexed, offsets / lens = the device index, n = min(c, cap)
+ * (n = 0 and slab_len = 0, pointers valid, before any poll and after a release).  The pointers stay
+ * valid and their contents stable until the next push that starts a step, poll, release, finish or
+ * close on the stream.  With the stream's device columns as chain columns this batch feeds
+ * pkt_pcap_write, pkt_compare_batch, pkt_edit_batch, pkt_to_vec_batch, pkt_extract_fields and
+ * pkt_set_fields* with no copy and no second parse.
+ * Errors name the call in pkt_pcap_stream_last_error; after a HIP or capture error, every later call
+ * returns it. */
 typedef struct pkt_pcap_stream pkt_pcap_stream_t;
 int         pkt_pcap_stream_open(int device, uint64_t max_bytes, uint64_t cap, int entry, const pkt_out_t *out,
                                  uint64_t step_bytes, pkt_pcap_stream_t **st);
 int         pkt_pcap_stream_push(pkt_pcap_stream_t *st, const uint8_t *bytes, uint64_t n);
 int         pkt_pcap_stream_poll(pkt_pcap_stream_t *st, uint64_t *n_records, uint64_t *offsets, uint32_t *lens);
 int         pkt_pcap_stream_finish(pkt_pcap_stream_t *st, uint64_t *n_records, uint64_t *offsets, uint32_t *lens);
+int         pkt_pcap_stream_release(pkt_pcap_stream_t *st, uint64_t n_records);
+int         pkt_pcap_stream_room(const pkt_pcap_stream_t *st, uint64_t *bytes);
+int         pkt_pcap_stream_released(const pkt_pcap_stream_t *st, uint64_t *records, uint64_t *bytes);
+int         pkt_pcap_stream_batch(pkt_pcap_stream_t *st, pkt_batch_t *batch);
 pkt_ctx_t  *pkt_pcap_stream_ctx(pkt_pcap_stream_t *st);
 const char *pkt_pcap_stream_last_error(const pkt_pcap_stream_t *st);
 int         pkt_pcap_stream_close(pkt_pcap_stream_t *st);

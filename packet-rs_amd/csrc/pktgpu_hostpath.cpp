@@ -1,5 +1,6 @@
 // pktgpu_hostpath.cpp — every path of the C ABI (include/pktgpu.h) that reads or writes host memory:
-// pkt_host_alloc / _free, pkt_parse_host, pkt_parse_pcap_host[_async / _result] and pkt_pcap_stream_*.
+// pkt_host_alloc / _free, pkt_parse_host, pkt_parse_pcap_host[_async / _result] and pkt_pcap_stream_* (the
+// window's release included).
 // Host code only: it launches no kernel of its own, but queues copies and the internal entries of
 // pktgpu_ctx.hpp (pktgpu_parse, the pcap indexer, the column export) on the ctx's three host streams.
 #include <hip/hip_runtime.h>
@@ -685,6 +686,11 @@ struct pkt_pcap_stream {
     bool stage_used[kStageSlots] = {};
     uint32_t cur = 0;   // the slot being filled
     uint64_t fill = 0;  // its bytes
+    // The window (include/pktgpu.h): ig is the ingest of the window's bytes, a capture of its own since the
+    // last release.  polled / polled_len: the count the last poll / finish returned and the bytes it had
+    // indexed (0 before the first and after a release); released_*: what pkt_pcap_stream_release has cut.
+    uint64_t polled = 0, polled_len = 0;
+    uint64_t released_records = 0, released_bytes = 0;
 };
 
 namespace {
@@ -706,6 +712,36 @@ int st_flush(pkt_pcap_stream* st) {
     st->cur = (c + 1) % pkt_pcap_stream::kStageSlots;
     st->fill = 0;
     return PKT_SUCCESS;
+}
+// poll / finish after their last step: wait, and remember what the window's index now holds.
+int st_wait(pkt_pcap_stream* st, uint64_t* n_records, uint64_t* offsets, uint32_t* lens) {
+    const int rc = ingest_wait(st->ig, n_records, offsets, lens);
+    if (rc == PKT_SUCCESS) {
+        st->polled = *n_records;
+        st->polled_len = st->ig.indexed;
+    }
+    return rc;
+}
+// Move hp.file[p, hi) down to hp.file + 24 on the copy stream (the streams are idle).  The ranges overlap
+// when the kept bytes outnumber the freed ones: forward chunks of at most p - 24 bytes are each disjoint
+// from their destination and never overwrite bytes a later chunk reads; past kMoveChunks of them, once
+// through a temporary buffer (*tmp, freed by the caller after the stream has drained).
+constexpr uint64_t kMoveChunks = 64;
+hipError_t st_move_down(HostPipe& hp, uint64_t p, uint64_t hi, void** tmp) {
+    const uint64_t kept = hi - p, d = p - 24;
+    if (!kept || !d) return hipSuccess;
+    hipStream_t s = hp.s[1];
+    if ((kept + d - 1) / d > kMoveChunks) {
+        hipError_t e = hipMalloc(tmp, kept);
+        if (e == hipSuccess) e = hipMemcpyAsync(*tmp, hp.file + p, kept, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp.file + 24, *tmp, kept, hipMemcpyDeviceToDevice, s);
+        return e;
+    }
+    for (uint64_t o = 0; o < kept; o += d) {
+        const hipError_t e = hipMemcpyAsync(hp.file + 24 + o, hp.file + p + o, std::min(d, kept - o), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 }  // namespace
 
@@ -790,7 +826,7 @@ int pkt_pcap_stream_poll(pkt_pcap_stream_t* st, uint64_t* n_records, uint64_t* o
     if (rc != PKT_SUCCESS) return st_ctx_fail(st, rc);
     if (st->ig.hi < 24) return st->ig.rc;  // not even the global header yet
     if (!st->done && st->ig.hi > st->ig.indexed) rc = ingest_step(st->ig, false);
-    if (rc == PKT_SUCCESS) rc = ingest_wait(st->ig, n_records, offsets, lens);
+    if (rc == PKT_SUCCESS) rc = st_wait(st, n_records, offsets, lens);
     return rc == PKT_SUCCESS ? rc : st_ctx_fail(st, rc);
 }
 
@@ -802,8 +838,72 @@ int pkt_pcap_stream_finish(pkt_pcap_stream_t* st, uint64_t* n_records, uint64_t*
     if (st->ig.hi < 24) return st_fail(st, PKT_ERR_INVALID_ARG, "pcap shorter than its global header");
     if (!st->done) rc = ingest_step(st->ig, true);  // the tail as pkt_pcap_index takes it (errors included)
     st->done = true;
-    if (rc == PKT_SUCCESS) rc = ingest_wait(st->ig, n_records, offsets, lens);
+    if (rc == PKT_SUCCESS) rc = st_wait(st, n_records, offsets, lens);
     return rc == PKT_SUCCESS ? rc : st_ctx_fail(st, rc);
+}
+
+// A release restarts the ingest on the kept bytes: they move down to offset 24 and the window becomes a
+// fresh capture of 24 + kept bytes already copied, whose first step (no carry-in) indexes and parses the kept
+// records again.  The cost is proportional to the kept bytes — one partial record for a consumer that
+// releases what it polled.
+int pkt_pcap_stream_release(pkt_pcap_stream_t* st, uint64_t n_records) {
+    if (!st) return PKT_ERR_INVALID_ARG;
+    if (st->done) return st_fail(st, PKT_ERR_INVALID_ARG, "release after finish");
+    if (n_records > std::min(st->polled, st->ig.cap))
+        return st_fail(st, PKT_ERR_INVALID_ARG, "release of more records than the last poll's columns hold");
+    Ingest& ig = st->ig;
+    if (ig.rc != PKT_SUCCESS) return st_ctx_fail(st, ig.rc);
+    if (!n_records) return PKT_SUCCESS;  // p = 24: the window stays as it is
+    pkt_ctx_t* ctx = st->ctx;
+    HostPipe& hp = ctx->hp;
+    int rc = st_flush(st);  // the staged bytes follow the kept ones
+    if (rc != PKT_SUCCESS) return st_ctx_fail(st, rc);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < HostPipe::kSlots && e == hipSuccess; k++) e = hipStreamSynchronize(hp.s[k]);
+    // the cut: the end of window record n - 1
+    uint64_t off = 0;
+    uint32_t len = 0;
+    if (e == hipSuccess) e = hipMemcpy(&off, hp.ioffs + (n_records - 1), 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&len, hp.ilens + (n_records - 1), 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return st_ctx_fail(st, ingest_fail(ig, hip_fail(ctx, e, "pkt_pcap_stream_release (cut)")));
+    const uint64_t p = off + len, hi = ig.hi;
+    if (p < 24 + 16 || p > st->polled_len || p > hi)  // (the index of a counted record: never)
+        return st_ctx_fail(st, ingest_fail(ig, fail(ctx, PKT_ERR_INVALID_ARG, "pkt_pcap_stream_release: bad cut")));
+    void* tmp = nullptr;
+    e = st_move_down(hp, p, hi, &tmp);
+    // the window as a fresh capture whose 24 + kept bytes are one landed copy
+    if (e == hipSuccess) e = hipEventRecord(hp.ev_copy[0], hp.s[1]);
+    if (e == hipSuccess) e = hipStreamSynchronize(hp.s[1]);
+    if (tmp) (void)hipFree(tmp);
+    if (e != hipSuccess) return st_ctx_fail(st, ingest_fail(ig, hip_fail(ctx, e, "pkt_pcap_stream_release (move)")));
+    ig.hi = 24 + (hi - p);
+    ig.indexed = 0;
+    ig.steps = 0;
+    ig.copies = 1;
+    ig.copy_end[0] = ig.hi;
+    st->released_records += n_records;
+    st->released_bytes += p - 24;
+    st->polled = st->polled_len = 0;
+    return PKT_SUCCESS;
+}
+
+int pkt_pcap_stream_room(const pkt_pcap_stream_t* st, uint64_t* bytes) {
+    if (!st || !bytes) return PKT_ERR_INVALID_ARG;
+    *bytes = st->max_bytes - st->ig.hi - st->fill;
+    return PKT_SUCCESS;
+}
+
+int pkt_pcap_stream_released(const pkt_pcap_stream_t* st, uint64_t* records, uint64_t* bytes) {
+    if (!st) return PKT_ERR_INVALID_ARG;
+    if (records) *records = st->released_records;
+    if (bytes) *bytes = st->released_bytes;
+    return PKT_SUCCESS;
+}
+
+int pkt_pcap_stream_batch(pkt_pcap_stream_t* st, pkt_batch_t* batch) {
+    if (!st || !batch) return PKT_ERR_INVALID_ARG;
+    *batch = pcap_host_batch(st->ctx->hp, st->polled_len, std::min(st->polled, st->ig.cap));
+    return PKT_SUCCESS;
 }
 
 pkt_ctx_t* pkt_pcap_stream_ctx(pkt_pcap_stream_t* st) { return st ? st->ctx : nullptr; }

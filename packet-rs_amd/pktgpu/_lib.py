@@ -182,6 +182,10 @@ SIGNATURES = {
     "pkt_pcap_stream_push": (ctypes.c_int, [_P, _P, ctypes.c_uint64]),
     "pkt_pcap_stream_poll": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), _P, _P]),
     "pkt_pcap_stream_finish": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), _P, _P]),
+    "pkt_pcap_stream_release": (ctypes.c_int, [_P, ctypes.c_uint64]),
+    "pkt_pcap_stream_room": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_pcap_stream_released": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_pcap_stream_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch)]),
     "pkt_pcap_stream_ctx": (_P, [_P]),
     "pkt_pcap_stream_last_error": (ctypes.c_char_p, [_P]),
     "pkt_pcap_stream_close": (ctypes.c_int, [_P]),

@@ -5,11 +5,23 @@ memory, a file read while it grows.  Each push appends bytes on the device; the 
 new bytes (from the first record the previous step could not count, kept in device words) and parses
 the records they complete into the stream's columns, while later bytes are still copying in.
 
-    >>> st = PcapStream(0, max_bytes=1 << 30, cap=1 << 20, columns="all")          # device columns
+The stream holds a WINDOW of the capture in max_bytes of device memory: the global header, then the bytes
+from the first unreleased record on.  Counts, offsets and columns are the window's; release(n) hands the
+first n records back, so an open-ended capture runs in bounded memory:
+
+    >>> st = PcapStream(0, max_bytes=64 << 20, cap=1 << 18, columns="all")         # device columns
     >>> for chunk in ring:                                                           # bytes / numpy u8
+    ...     if len(chunk) > st.room():                                               # the window is full
+    ...         c, _ = st.poll()
+    ...         m = min(c, st.cap)
+    ...         slab, offs, lens = st.batch()                                        # the packets, on the device
+    ...         consume(st.out["ipv4_src"][:m], slab, offs, lens)                    # e.g. Parser.pcap_write(slab, offsets=offs, lens=lens)
+    ...         st.release()                                                         # every record just polled
     ...     st.push(chunk)
-    >>> n, (offs, lens) = st.finish()
-    >>> st.out["ipv4_src"][:n]                                                       # torch tensor
+    >>> n, (offs, lens) = st.finish()                                                # the last window
+    >>> st.released()                                                                # (records, bytes) handed back before it
+
+A stream that never releases is one capture of at most max_bytes held whole.
 """
 import ctypes
 
@@ -50,6 +62,9 @@ class PcapStream:
         if rc != 0:
             raise RuntimeError(f"pkt_pcap_stream_open failed ({rc})")
         self._st = h
+        self._dev = int(device)
+        self._polled = 0
+        self.aliased = None  # set by batch()
 
     def _check(self, rc, what):
         if rc != 0:
@@ -72,6 +87,7 @@ class PcapStream:
         self._check(fn(self._st, ctypes.byref(n), offs.ctypes.data if index else None,
                        lens.ctypes.data if index else None), what)
         m = min(n.value, self.cap)
+        self._polled = m
         return n.value, ((offs[:m], lens[:m]) if index else None)
 
     def poll(self, index=False):
@@ -81,6 +97,53 @@ class PcapStream:
     def finish(self, index=True):
         """End of capture: the tail as pkt_pcap_index takes it -> (n, (offsets, lens))."""
         return self._counted(self._L.pkt_pcap_stream_finish, "pkt_pcap_stream_finish", index)
+
+    def release(self, n=None):
+        """pkt_pcap_stream_release: the consumer is done with window records [0, n) (None: every record of
+        the last poll that the columns hold).  The columns, the index and batch()'s tensors restart at
+        the next poll: what they held is stale after this call.  Blocking."""
+        n = self._polled if n is None else int(n)
+        self._check(self._L.pkt_pcap_stream_release(self._st, n), "pkt_pcap_stream_release")
+        if n:
+            self._polled = 0
+
+    def room(self):
+        """Bytes a push can take now (max_bytes minus the window's bytes)."""
+        b = ctypes.c_uint64()
+        self._check(self._L.pkt_pcap_stream_room(self._st, ctypes.byref(b)), "pkt_pcap_stream_room")
+        return b.value
+
+    def released(self):
+        """(records, bytes) released so far: window record i is capture record i + records, window offset
+        w is capture offset w + bytes."""
+        r, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._L.pkt_pcap_stream_released(self._st, ctypes.byref(r), ctypes.byref(b)),
+                    "pkt_pcap_stream_released")
+        return r.value, b.value
+
+    def batch(self):
+        """pkt_pcap_stream_batch: the window as of the last poll / finish as an indexed device batch ->
+        (slab uint8, offsets uint64, lens uint32), torch tensors that ALIAS the stream's device memory (no
+        copy; `aliased` is set True once that has been checked against the ABI's pointers), so
+        Parser.pcap_write(slab, offsets=offsets, lens=lens) and its siblings take them directly.  They stay
+        valid, and their contents stable, until the next push that starts a step, poll, release, finish
+        or close.  Should a torch build copy instead of aliasing, the tensors are device copies of the same
+        bytes (`aliased` False): still correct, at the price of the copy."""
+        torch = _torch()
+        b = self._lib.PktBatch()
+        self._check(self._L.pkt_pcap_stream_batch(self._st, ctypes.byref(b)), "pkt_pcap_stream_batch")
+        dev = torch.device("cuda", self._dev)
+        n = int(b.n)
+
+        def alias(ptr, nbytes, dtype):
+            if not nbytes:
+                return torch.empty(0, dtype=dtype, device=dev)
+            t = torch.as_tensor(_DeviceBytes(self, ptr, nbytes), device=dev)
+            self.aliased = t.data_ptr() == ptr
+            return t.view(dtype)
+
+        return (alias(b.slab, int(b.slab_len), torch.uint8), alias(b.offsets, n * 8, torch.uint64),
+                alias(b.lens, n * 4, torch.uint32))
 
     def close(self):
         if getattr(self, "_st", None):
@@ -95,6 +158,16 @@ class PcapStream:
             self.close()
         except Exception:
             pass
+
+
+class _DeviceBytes:
+    """`nbytes` of device memory at `ptr` for torch.as_tensor (the CUDA array interface); keeps the
+    stream that owns the memory referenced while a tensor made from it lives."""
+
+    def __init__(self, owner, ptr, nbytes):
+        self._owner = owner
+        self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
 
 
 def _size(v):
