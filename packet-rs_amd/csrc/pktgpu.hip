@@ -396,9 +396,7 @@ __device__ __forceinline__ void parse_block(const KParams& p, uint32_t blk, uint
             w[2] = v.z;
             w[3] = v.w;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         PKT_STAMP(1);
         parse_tile<NCH, GM, WK, true, LATE>(p, lds, base, chunk, off, len, act, pkt_st, T, mb);
         return;
@@ -826,9 +824,9 @@ int parse_impl(pkt_ctx_t* ctx, const pkt_batch_t* b, int entry, const pkt_out_t*
     if (entry < 0 || entry >= PKT_ENTRY_COUNT) return fail(ctx, PKT_ERR_INVALID_ARG, "bad entry");
     if (b->n == 0) return PKT_SUCCESS;
     if (!b->slab) return fail(ctx, PKT_ERR_INVALID_ARG, "null slab");
-    if (((uintptr_t)b->slab & 15) != 0) return fail(ctx, PKT_ERR_INVALID_ARG, "slab not 16-byte aligned");
-    if (b->offsets && !b->lens) return fail(ctx, PKT_ERR_INVALID_ARG, "offsets without lens");
-    if (!b->offsets && b->stride == 0) return fail(ctx, PKT_ERR_INVALID_ARG, "stride 0");
+    int rc = check_batch_slab16(ctx, b);
+    if (rc == PKT_SUCCESS) rc = check_batch_index(ctx, b);
+    if (rc != PKT_SUCCESS) return rc;
     if (out->ipv6_src && ((uintptr_t)out->ipv6_src & 15)) return fail(ctx, PKT_ERR_INVALID_ARG, "ipv6_src not 16-byte aligned");
     if (out->ipv6_dst && ((uintptr_t)out->ipv6_dst & 15)) return fail(ctx, PKT_ERR_INVALID_ARG, "ipv6_dst not 16-byte aligned");
     if (b->slab_len == 0) return fail(ctx, PKT_ERR_INVALID_ARG, "slab_len 0");

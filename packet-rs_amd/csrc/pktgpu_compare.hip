@@ -4,9 +4,9 @@
 //                     (m = the common length, chunks = ceil(m / 16)) and, with ignores, resolves every
 //                     spec against its chain into a packet-relative bit range in LDS.  A wave prefix sum
 //                     of the chunk counts goes to LDS and the wave walks the FLATTENED chunk list, 64
-//                     chunks per step and kCmpQ steps' loads in flight: a lane finds its (pair, chunk) by
-//                     a search in the prefix, builds its 16 packet-relative bytes of a and of b from two
-//                     aligned 16-byte loads each (the two sides differ in alignment), and adds the
+//                     chunks per step and kCmpQ steps' loads in flight: a lane finds its (pair, chunk) in
+//                     the prefix, builds its 16 packet-relative bytes of a and of b from two aligned
+//                     16-byte loads each (the two sides differ in alignment), and adds the
 //                     chunk's matching bytes / takes the minimum of its first differing byte in the
 //                     pair's LDS slot.  A 65535-byte pair among 64-byte ones costs its bytes, not 64
 //                     times its length.  Lane p then writes pair p's three outputs (coalesced) and the
@@ -29,16 +29,8 @@ constexpr uint32_t kCmpMaxIgnore = 16;
 constexpr uint32_t kCmpSlots = 256;     // summary slots the blocks spread their atomics over
 constexpr uint32_t kCmpSlotWords = 16;  // a slot: [n_equal, n_len, n_bytes, ~first_bad] on 128 bytes of its own
 
-struct CSide {
-    const uint8_t* slab;
-    uint64_t slab_len;
-    const uint64_t* offsets;
-    const uint32_t* lens;
-    uint32_t stride;
-};
-
 struct CParams {
-    CSide a, b;
+    BatchSrc a, b;
     uint64_t n;  // < 2^32
     const uint8_t* n_hdrs;
     const uint8_t* hdr_type;   // [PKT_MAX_HDRS][n]
@@ -51,50 +43,9 @@ struct CParams {
     pkt_field_spec_t ign[kCmpMaxIgnore];
 };
 
-__device__ __forceinline__ uint64_t c_off(const CSide& s, uint64_t i) { return s.offsets ? s.offsets[i] : i * s.stride; }
-
-// pkt_batch_t's packet length: clamped to the slab end and to 65535
-__device__ __forceinline__ uint32_t c_len(const CSide& s, uint64_t i, uint64_t off) {
-    uint32_t l = s.lens ? s.lens[i] : s.stride;
-    const uint64_t room = off < s.slab_len ? s.slab_len - off : 0;
-    l = l > room ? (uint32_t)room : l;
-    return l > 65535u ? 65535u : l;
-}
-
-struct U128 {
-    uint64_t lo, hi;
-};
-
-// ones in bits [0, k), k in 0..128
-__device__ __forceinline__ U128 bits_below(uint32_t k) {
-    const uint64_t lo = k >= 64 ? ~0ull : (1ull << k) - 1;
-    const uint64_t hi = k <= 64 ? 0ull : k >= 128 ? ~0ull : (1ull << (k - 64)) - 1;
-    return U128{lo, hi};
-}
-
-// o = the 16 bytes at (aligned address of v0) + sh, sh in 0..15, of the 32 bytes v0 | v1: two rounds of
-// dword selects by sh's bits 2 and 3, then one v_alignbyte per dword
-__device__ __forceinline__ void take16(uint4 v0, uint4 v1, uint32_t sh, uint32_t o[4]) {
-    const bool b2 = sh & 4u, b3 = sh & 8u;
-    const uint32_t t0 = b2 ? v0.y : v0.x, t1 = b2 ? v0.z : v0.y, t2 = b2 ? v0.w : v0.z, t3 = b2 ? v1.x : v0.w;
-    const uint32_t t4 = b2 ? v1.y : v1.x, t5 = b2 ? v1.z : v1.y, t6 = b2 ? v1.w : v1.z;
-    const uint32_t u0 = b3 ? t2 : t0, u1 = b3 ? t3 : t1, u2 = b3 ? t4 : t2, u3 = b3 ? t5 : t3, u4 = b3 ? t6 : t4;
-    const uint32_t r = sh & 3u;
-    o[0] = __builtin_amdgcn_alignbyte(u1, u0, r);
-    o[1] = __builtin_amdgcn_alignbyte(u2, u1, r);
-    o[2] = __builtin_amdgcn_alignbyte(u3, u2, r);
-    o[3] = __builtin_amdgcn_alignbyte(u4, u3, r);
-}
-
 // bit 7 of every byte of x that is not zero
 __device__ __forceinline__ uint32_t nonzero_bytes(uint32_t x) {
     return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // The ignore ranges of a wave's pairs: [spec][64] first and last ignored bit, packet-relative (first >
@@ -117,21 +68,16 @@ __global__ __launch_bounds__(kCmpBlock) void cmp_kernel(CParams P) {
     uint64_t ao = 0, bo = 0;
     uint32_t la = 0, lb = 0;
     if (in) {
-        ao = c_off(P.a, i);
-        bo = c_off(P.b, i);
-        la = c_len(P.a, i, ao);
-        lb = c_len(P.b, i, bo);
+        ao = pkt_off(P.a, i);
+        bo = pkt_off(P.b, i);
+        la = pkt_len(P.a, i, ao);
+        lb = pkt_len(P.b, i, bo);
     }
     const uint32_t m = la < lb ? la : lb;
     const uint32_t chunks = (m + 15u) >> 4;
-    uint32_t x = chunks;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
+    const uint32_t incl = wave_incl_scan(chunks, lane);
     if (lane == 0) s_pre[wv][0] = 0;
-    s_pre[wv][lane + 1] = x;
+    s_pre[wv][lane + 1] = incl;
     s_ao[wv][lane] = ao;
     s_bo[wv][lane] = bo;
     s_m[wv][lane] = m;
@@ -169,11 +115,7 @@ __global__ __launch_bounds__(kCmpBlock) void cmp_kernel(CParams P) {
     }
     __syncthreads();  // (also orders s_sum's first values before the atomics at the end)
     const uint32_t total = __builtin_amdgcn_readfirstlane(s_pre[wv][64]);  // <= 64 * 4096
-    // Every pair of the wave with the same chunk count c (a batch of equal-length packets): chunk f is
-    // pair f / c, by a multiplication (exact for f < 2^18, c <= 4096); otherwise a search in the prefix.
-    const uint32_t c_uni = __builtin_amdgcn_readfirstlane(chunks);
-    const bool uni = c_uni > 1 && __ballot(chunks == c_uni) == ~0ull;
-    const uint32_t magic = uni ? 0xFFFFFFFFu / c_uni + 1u : 0u;
+    const FlatWalk walk = flat_walk(chunks);
     // an aligned chunk at or past the slab's last one is not loaded again: its bytes are not needed
     const uint64_t a_last = P.a.slab_len ? ((P.a.slab_len + 15) & ~(uint64_t)15) - 16 : 0;
     const uint64_t b_last = P.b.slab_len ? ((P.b.slab_len + 15) & ~(uint64_t)15) - 16 : 0;
@@ -187,18 +129,8 @@ __global__ __launch_bounds__(kCmpBlock) void cmp_kernel(CParams P) {
             ck[q] = sha[q] = shb[q] = 0;
             a0[q] = a1[q] = b0[q] = b1[q] = make_uint4(0, 0, 0, 0);
             if (f >= total) continue;
-            uint32_t p, k;
-            if (uni) {
-                p = __umulhi(f, magic);
-                k = f - p * c_uni;
-            } else {
-                // the pair holding flat chunk f: the number of prefix ends at or below f
-                p = 0;
-#pragma unroll
-                for (uint32_t st = 32; st; st >>= 1)
-                    if (s_pre[wv][p + st] <= f) p += st;
-                k = f - s_pre[wv][p];
-            }
+            const FlatAt at = locate(walk, s_pre[wv], f);
+            const uint32_t p = at.p, k = at.k;
             pr[q] = p;
             ck[q] = k;
             // Bytes [16 k, min(16 k + 16, m)) of both packets lie inside their slabs, so the first aligned
@@ -228,12 +160,12 @@ __global__ __launch_bounds__(kCmpBlock) void cmp_kernel(CParams P) {
                 // the ranges that touch the chunk's bits [128 k, 128 k + 127], MSB-first: bit t of the
                 // chunk is bit 127 - t of a 128-bit word, whose bytes are then reversed into memory order
                 const uint32_t c0 = 128u * k;
-                U128 g{0, 0};
+                Le128 g{0, 0};
                 for (uint32_t s = 0; s < P.nignore; s++) {
                     const uint32_t lo = ig[s * 128u + p], hi = ig[s * 128u + 64u + p];
                     if (lo > hi || hi < c0 || lo > c0 + 127u) continue;
                     const uint32_t l = lo > c0 ? lo - c0 : 0u, h = hi < c0 + 127u ? hi - c0 : 127u;
-                    const U128 up = bits_below(128u - l), dn = bits_below(127u - h);
+                    const Le128 up = bits_below(128u - l), dn = bits_below(127u - h);
                     g.lo |= up.lo & ~dn.lo;
                     g.hi |= up.hi & ~dn.hi;
                 }
@@ -319,19 +251,11 @@ __global__ __launch_bounds__(kCmpSlots) void cmp_fin_kernel(uint64_t* __restrict
     }
 }
 
-int side(pkt_ctx_t* ctx, const pkt_batch_t* b, CSide& s) {
-    if (b->n) {
-        if (b->slab_len && !b->slab) return fail(ctx, PKT_ERR_INVALID_ARG, "null slab");
-        if ((uintptr_t)b->slab & 15) return fail(ctx, PKT_ERR_INVALID_ARG, "slab not 16-byte aligned");
-        if (b->offsets && !b->lens) return fail(ctx, PKT_ERR_INVALID_ARG, "offsets without lens");
-        if (!b->offsets && b->stride == 0) return fail(ctx, PKT_ERR_INVALID_ARG, "stride 0");
-    }
-    s.slab = b->slab;
-    s.slab_len = b->slab_len;
-    s.offsets = b->offsets;
-    s.lens = b->lens;
-    s.stride = b->stride;
-    return PKT_SUCCESS;
+int side(pkt_ctx_t* ctx, const pkt_batch_t* b, BatchSrc& s) {
+    s = batch_src(b);
+    if (!b->n) return PKT_SUCCESS;
+    const int rc = check_batch_slab16(ctx, b);
+    return rc != PKT_SUCCESS ? rc : check_batch_index(ctx, b);
 }
 
 // The two launches, queued on s.  The summary arrives in ctx->cmp.ctl once the stream has passed them.

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/pktgpu.h"
+#include "pktgpu_batch.hpp"
 
 // Device buffers and streams of the host-memory pipeline (pkt_parse_host), grown on demand.
 struct HostPipe {
@@ -161,6 +162,17 @@ struct pkt_ctx {
 inline int fail(pkt_ctx* ctx, int code, const char* msg) {
     if (ctx) ctx->err = msg;
     return code;
+}
+
+// The pkt_batch_t refusals of a batch with n > 0 (the rules and their texts: pktgpu_batch.hpp).  An entry point
+// applies the ones its kernels need, in its own order, next to the refusals only it has.
+inline int check_batch_index(pkt_ctx* ctx, const pkt_batch_t* b) {
+    const char* msg = batch_index_error(b);
+    return msg ? fail(ctx, PKT_ERR_INVALID_ARG, msg) : PKT_SUCCESS;
+}
+inline int check_batch_slab16(pkt_ctx* ctx, const pkt_batch_t* b) {
+    const char* msg = batch_slab16_error(b);
+    return msg ? fail(ctx, PKT_ERR_INVALID_ARG, msg) : PKT_SUCCESS;
 }
 
 inline int hip_fail(pkt_ctx* ctx, hipError_t e, const char* what) {

@@ -33,14 +33,10 @@ constexpr uint32_t kEdRows = PKT_MAX_HDRS + 1;    // list: 16 entries and the 17
 constexpr uint32_t kEdConst = (16 + kEdData + 32) / 16;  // hdr_data in LDS: 16 bytes in front, 32 behind (uint4)
 constexpr uint32_t kKonst = 0x80000000u;          // entry / segment: the bytes are hdr_data's
 
-__constant__ uint8_t kEdHdrSize[PKT_HDR_COUNT] = {0, 14, 4, 20, 40, 4, 20, 8, 28, 8, 14, 3, 5, 4, 4, 4, 4, 8, 12, 8, 35, 4};
-const uint8_t kEdHdrSizeHost[PKT_HDR_COUNT] = {0, 14, 4, 20, 40, 4, 20, 8, 28, 8, 14, 3, 5, 4, 4, 4, 4, 8, 12, 8, 35, 4};
+__constant__ uint8_t kEdHdrSize[PKT_HDR_COUNT] = PKT_HDR_SIZE_LIST;
 
 struct EParams {
-    const uint8_t* slab;
-    uint64_t slab_len;
-    const uint64_t* offsets;
-    const uint32_t* lens;
+    BatchSrc src;
     uint64_t n;  // < 2^32
     const uint8_t* status;
     const uint8_t* n_hdrs;
@@ -61,32 +57,13 @@ struct EParams {
     uint16_t* o_payload_off;
     uint16_t* o_payload_len;
     uint32_t* o_hdr_mask;
-    uint32_t stride, slot, nops, reserved;
+    uint32_t slot, nops;
     pkt_edit_op_t ops[kEdMaxOps];
     uint32_t data[kEdData / 4];
 };
 
-// o = the 16 bytes at (aligned address of v0) + sh, sh in 0..15, of the 32 bytes v0 | v1
-__device__ __forceinline__ void take16(uint4 v0, uint4 v1, uint32_t sh, uint32_t o[4]) {
-    const bool b2 = sh & 4u, b3 = sh & 8u;
-    const uint32_t t0 = b2 ? v0.y : v0.x, t1 = b2 ? v0.z : v0.y, t2 = b2 ? v0.w : v0.z, t3 = b2 ? v1.x : v0.w;
-    const uint32_t t4 = b2 ? v1.y : v1.x, t5 = b2 ? v1.z : v1.y, t6 = b2 ? v1.w : v1.z;
-    const uint32_t u0 = b3 ? t2 : t0, u1 = b3 ? t3 : t1, u2 = b3 ? t4 : t2, u3 = b3 ? t5 : t3, u4 = b3 ? t6 : t4;
-    const uint32_t r = sh & 3u;
-    o[0] = __builtin_amdgcn_alignbyte(u1, u0, r);
-    o[1] = __builtin_amdgcn_alignbyte(u2, u1, r);
-    o[2] = __builtin_amdgcn_alignbyte(u3, u2, r);
-    o[3] = __builtin_amdgcn_alignbyte(u4, u3, r);
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ones in bytes [0, k) of a dword, k in 0..4
-__device__ __forceinline__ uint32_t bytes_below(uint32_t k) { return k >= 4u ? ~0u : (1u << (8u * k)) - 1u; }
+__device__ __forceinline__ uint32_t dword_bytes_below(uint32_t k) { return k >= 4u ? ~0u : (1u << (8u * k)) - 1u; }
 
 // the part of the chunk's byte range [l, h) (0 <= l <= h <= 16) inside dword d, as dword-relative [lo, hi)
 __device__ __forceinline__ void dword_range(uint32_t l, uint32_t h, uint32_t d, uint32_t& lo, uint32_t& hi) {
@@ -157,7 +134,7 @@ __device__ __forceinline__ void merge(const Piece& x, uint32_t out[4]) {
     for (uint32_t d = 0; d < 4; d++) {
         uint32_t l, h;
         dword_range(x.ml, x.mh, d, l, h);
-        out[d] |= v[d] & (bytes_below(h) & ~bytes_below(l));
+        out[d] |= v[d] & (dword_bytes_below(h) & ~dword_bytes_below(l));
     }
 }
 
@@ -215,34 +192,26 @@ __global__ __launch_bounds__(kEdBlock) void edit_kernel(EParams P) {
     uint32_t hb = 0;  // the list's bytes
     bool run = false;
     if (in) {
-        off = P.offsets ? P.offsets[i] : i * P.stride;
-        uint32_t l = P.lens ? P.lens[i] : P.stride;
-        const uint64_t left = off < P.slab_len ? P.slab_len - off : 0;
-        l = l > left ? (uint32_t)left : l;
-        len = l > 65535u ? 65535u : l;
+        off = pkt_off(P.src, i);
+        len = pkt_len(P.src, i, off);
         o = P.dst_offsets ? P.dst_offsets[i] : i * P.slot;
         const uint64_t dl = o < P.dst_len ? P.dst_len - o : 0;
         room = dl < P.slot ? (uint32_t)dl : P.slot;
         src_status = P.status[i];
-        uint32_t nh = P.n_hdrs[i];
+        // n_hdrs and the first four slot rows with the loads above and below, whatever n_hdrs is: one round trip
+        // for the common chains; later rows only where a chain has them
+        const ChainPre cp = chain_load(P, i);
+        uint32_t nh = cp.nh;
         const uint32_t po = P.payload_off[i], pl = P.payload_len[i];
         run = P.select ? P.select[i] != 0 : true;
-        // the first four slot rows with the loads above, whatever n_hdrs is (the columns hold 16 rows): one
-        // round trip for the common chains; later rows only where a chain has them
-        uint32_t ty4[4], ho4[4];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) {
-            ty4[j] = P.hdr_type[(uint64_t)j * P.n + i];
-            ho4[j] = P.hdr_off[(uint64_t)j * P.n + i];
-        }
         if (src_status == PKT_OK) {
             st = PKT_EDIT_OK;
             nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
             for (uint32_t j = 0; j < nh; j++) {
                 uint32_t ty, ho;
                 if (j < 4) {
-                    ty = j == 0 ? ty4[0] : j == 1 ? ty4[1] : j == 2 ? ty4[2] : ty4[3];
-                    ho = j == 0 ? ho4[0] : j == 1 ? ho4[1] : j == 2 ? ho4[2] : ho4[3];
+                    ty = j == 0 ? cp.ty[0] : j == 1 ? cp.ty[1] : j == 2 ? cp.ty[2] : cp.ty[3];
+                    ho = j == 0 ? cp.of[0] : j == 1 ? cp.of[1] : j == 2 ? cp.of[2] : cp.of[3];
                 } else {
                     ty = P.hdr_type[(uint64_t)j * P.n + i];
                     ho = P.hdr_off[(uint64_t)j * P.n + i];
@@ -344,22 +313,15 @@ __global__ __launch_bounds__(kEdBlock) void edit_kernel(EParams P) {
 
     // ---- phase 2: the wave's aligned destination chunks, flattened
     const uint32_t chunks = total ? (((uint32_t)o & 15u) + total + 15u) >> 4 : 0u;
-    uint32_t x = chunks;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
+    const uint32_t incl = wave_incl_scan(chunks, lane);
     if (lane == 0) s_pre[wv][0] = 0;
-    s_pre[wv][lane + 1] = x;
+    s_pre[wv][lane + 1] = incl;
     s_src[wv][lane] = off;
     s_dst[wv][lane] = o;
     s_tot[wv][lane] = total | ns << 16;
     wave_sync();
     const uint32_t all = __builtin_amdgcn_readfirstlane(s_pre[wv][64]);  // <= 64 * 4097
-    const uint32_t c_uni = __builtin_amdgcn_readfirstlane(chunks);
-    const bool uni = c_uni > 1 && __ballot(chunks == c_uni) == ~0ull;
-    const uint32_t magic = uni ? 0xFFFFFFFFu / c_uni + 1u : 0u;
+    const FlatWalk walk = flat_walk(chunks);
     const Wave W{s_la[wv], s_lb[wv], s_src[wv], s_konst};
     for (uint32_t base = 0; base < all; base += 64u * kEdQ) {  // uniform
         Piece pc[kEdQ][2];
@@ -375,17 +337,8 @@ __global__ __launch_bounds__(kEdBlock) void edit_kernel(EParams P) {
             at[q] = nullptr;
             pc[q][0] = pc[q][1] = Piece{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), 0, 0, 0};
             if (f >= all) continue;
-            uint32_t p, k;
-            if (uni) {
-                p = __umulhi(f, magic);
-                k = f - p * c_uni;
-            } else {
-                p = 0;
-#pragma unroll
-                for (uint32_t stp = 32; stp; stp >>= 1)
-                    if (s_pre[wv][p + stp] <= f) p += stp;
-                k = f - s_pre[wv][p];
-            }
+            const FlatAt pk = locate(walk, s_pre[wv], f);
+            const uint32_t p = pk.p, k = pk.k;
             const uint64_t d = s_dst[wv][p];
             const uint32_t tn = s_tot[wv][p], tot = tn & 0xFFFFu, nsp = tn >> 16;
             const int32_t c = (int32_t)(16u * k) - (int32_t)((uint32_t)d & 15u);
@@ -400,8 +353,8 @@ __global__ __launch_bounds__(kEdBlock) void edit_kernel(EParams P) {
             hi[q] = h;
             c0[q] = c;
             at[q] = P.dst + (d & ~(uint64_t)15) + 16ull * k;
-            pc[q][0] = fetch(W, P.slab, p, s, nsp, c, l, h);
-            pc[q][1] = fetch(W, P.slab, p, s + 1u, nsp, c, l, h);
+            pc[q][0] = fetch(W, P.src.slab, p, s, nsp, c, l, h);
+            pc[q][1] = fetch(W, P.src.slab, p, s + 1u, nsp, c, l, h);
         }
 #pragma unroll
         for (uint32_t q = 0; q < kEdQ; q++) {
@@ -411,7 +364,7 @@ __global__ __launch_bounds__(kEdBlock) void edit_kernel(EParams P) {
             merge(pc[q][1], out);
             for (uint32_t s = s0[q] + 2u; s < nsq[q]; s++) {  // a chunk of three or more segments
                 if (s_lb[wv][(s - 1u) * 64u + pr[q]] >= hi[q]) break;
-                const Piece more = fetch(W, P.slab, pr[q], s, nsq[q], c0[q], lo[q], hi[q]);
+                const Piece more = fetch(W, P.src.slab, pr[q], s, nsq[q], c0[q], lo[q], hi[q]);
                 merge(more, out);
             }
             put_chunk(at[q], out, (uint32_t)((int32_t)lo[q] - c0[q]), (uint32_t)((int32_t)hi[q] - c0[q]));
@@ -436,7 +389,7 @@ extern "C" int pkt_edit_batch(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_ou
         if (ops[k].kind != PKT_EDIT_INSERT) continue;
         if (ops[k].hdr_type == 0 || ops[k].hdr_type >= PKT_HDR_COUNT)
             return fail(ctx, PKT_ERR_INVALID_ARG, "pkt_edit_batch: insert of an unknown header type");
-        if (!hdr_data || (uint64_t)ops[k].data_off + kEdHdrSizeHost[ops[k].hdr_type] > hdr_data_len)
+        if (!hdr_data || (uint64_t)ops[k].data_off + (uint32_t)pkt_hdr_size(ops[k].hdr_type) > hdr_data_len)
             return fail(ctx, PKT_ERR_INVALID_ARG, "pkt_edit_batch: an insert's bytes run past hdr_data_len");
     }
     if (b->n == 0) return PKT_SUCCESS;
@@ -444,18 +397,13 @@ extern "C" int pkt_edit_batch(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_ou
         !parsed->payload_len)
         return fail(ctx, PKT_ERR_INVALID_ARG, "pkt_edit_batch: null dst or chain column");
     if ((uintptr_t)dst & 15) return fail(ctx, PKT_ERR_INVALID_ARG, "pkt_edit_batch: dst not 16-byte aligned");
-    if (b->slab_len && !b->slab) return fail(ctx, PKT_ERR_INVALID_ARG, "null slab");
-    if ((uintptr_t)b->slab & 15) return fail(ctx, PKT_ERR_INVALID_ARG, "slab not 16-byte aligned");
-    if (b->offsets && !b->lens) return fail(ctx, PKT_ERR_INVALID_ARG, "offsets without lens");
-    if (!b->offsets && b->stride == 0) return fail(ctx, PKT_ERR_INVALID_ARG, "stride 0");
+    int rc = check_batch_slab16(ctx, b);
+    if (rc == PKT_SUCCESS) rc = check_batch_index(ctx, b);
+    if (rc != PKT_SUCCESS) return rc;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     EParams P{};
-    P.slab = b->slab;
-    P.slab_len = b->slab_len;
-    P.offsets = b->offsets;
-    P.lens = b->lens;
-    P.stride = b->stride;
+    P.src = batch_src(b);
     P.n = b->n;
     P.status = parsed->status;
     P.n_hdrs = parsed->n_hdrs;

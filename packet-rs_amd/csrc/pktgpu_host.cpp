@@ -1,9 +1,9 @@
 // pktgpu_host.cpp — host-side part of the C ABI: metadata tables, the pcap indexer and the
 // host checksum.  No device code.
 #include <cstring>
-#include <initializer_list>
 
 #include "../../include/pktgpu.h"
+#include "pktgpu_batch.hpp"
 
 namespace {
 
@@ -19,7 +19,7 @@ struct HdrDef {
 };
 
 // make_header! invocations of the reference (src/headers.rs:529-827).
-const HdrDef kHdrs[PKT_HDR_COUNT] = {
+constexpr HdrDef kHdrs[PKT_HDR_COUNT] = {
     {"", 0, 0, {}},
     {"Ether", 14, 3, {{"dst", 0, 47}, {"src", 48, 95}, {"etype", 96, 111}}},
     {"Vlan", 4, 4, {{"pcp", 0, 2}, {"cfi", 3, 3}, {"vid", 4, 15}, {"etype", 16, 31}}},
@@ -67,6 +67,16 @@ const HdrDef kHdrs[PKT_HDR_COUNT] = {
       {"fwd_delay", 264, 279}}},
     {"MPLS", 4, 4, {{"label", 0, 19}, {"exp", 20, 22}, {"bos", 23, 23}, {"ttl", 24, 31}}},
 };
+
+constexpr bool sizes_agree() {
+    for (int t = 0; t < PKT_HDR_COUNT; t++)
+        if (kHdrs[t].size != kHdrSizes[t]) return false;
+    return true;
+}
+static_assert(sizes_agree(), "kHdrs[].size and PKT_HDR_SIZE_LIST (pktgpu_batch.hpp) differ");
+
+// a host model's refusal of a batch with n > 0: the device entry points' rules, less the slab's alignment
+bool bad_batch(const pkt_batch_t* b) { return batch_null_slab(b) || batch_index_error(b); }
 
 const char* kEntryNames[PKT_ENTRY_COUNT] = {
     "parse", "parse_dot3", "parse_llc", "parse_snap", "parse_ethernet", "parse_vlan",
@@ -139,14 +149,11 @@ int pkt_pcap_write_host(const pkt_batch_t* b, const uint8_t* select, uint32_t sn
     if (bytes_out) *bytes_out = 0;
     if (n_out) *n_out = 0;
     if (!b || b->n >= (1ull << 32) || (dst_len && !dst)) return PKT_ERR_INVALID_ARG;
-    if (b->n && ((b->slab_len && !b->slab) || (b->offsets && !b->lens) || (!b->offsets && b->stride == 0)))
-        return PKT_ERR_INVALID_ARG;
+    if (b->n && bad_batch(b)) return PKT_ERR_INVALID_ARG;
+    const BatchSrc src = batch_src(b);
     auto pkt = [&](uint64_t i, uint64_t& off, uint32_t& len, uint32_t& incl) {
-        off = b->offsets ? b->offsets[i] : i * b->stride;
-        const uint64_t room = off < b->slab_len ? b->slab_len - off : 0;
-        uint64_t l = b->lens ? b->lens[i] : b->stride;
-        l = l > room ? room : l;
-        len = l > 65535 ? 65535u : (uint32_t)l;
+        off = pkt_off(src, i);
+        len = pkt_len(src, i, off);
         incl = snaplen && len > snaplen ? snaplen : len;
     };
     uint64_t total = 24, cnt = 0;
@@ -192,22 +199,18 @@ int pkt_compare_host(const pkt_batch_t* a, const pkt_batch_t* b, const pkt_chain
     for (uint32_t k = 0; k < nignore; k++)
         if (ignore[k].end < ignore[k].start) return PKT_ERR_INVALID_ARG;
     const uint64_t n = a->n;
-    for (const pkt_batch_t* s : {a, b})
-        if (n && ((s->slab_len && !s->slab) || (s->offsets && !s->lens) || (!s->offsets && s->stride == 0)))
-            return PKT_ERR_INVALID_ARG;
-    auto pkt = [](const pkt_batch_t* s, uint64_t i, uint32_t& len) -> const uint8_t* {
-        const uint64_t off = s->offsets ? s->offsets[i] : i * s->stride;
-        const uint64_t room = off < s->slab_len ? s->slab_len - off : 0;
-        uint64_t l = s->lens ? s->lens[i] : s->stride;
-        l = l > room ? room : l;
-        len = l > 65535 ? 65535u : (uint32_t)l;
-        return len ? s->slab + off : nullptr;
+    if (n && (bad_batch(a) || bad_batch(b))) return PKT_ERR_INVALID_ARG;
+    const BatchSrc sa = batch_src(a), sb = batch_src(b);
+    auto pkt = [](const BatchSrc& s, uint64_t i, uint32_t& len) -> const uint8_t* {
+        const uint64_t off = pkt_off(s, i);
+        len = pkt_len(s, i, off);
+        return len ? s.slab + off : nullptr;
     };
     pkt_cmp_summary_t sum{0, 0, 0, n};
     for (uint64_t i = 0; i < n; i++) {
         uint32_t la, lb;
-        const uint8_t* pa = pkt(a, i, la);
-        const uint8_t* pb = pkt(b, i, lb);
+        const uint8_t* pa = pkt(sa, i, la);
+        const uint8_t* pb = pkt(sb, i, lb);
         const uint32_t m = la < lb ? la : lb;
         // the specs' bit ranges in packet i, first > last where its chain lacks the header
         uint32_t lo[16], hi[16];
@@ -268,17 +271,15 @@ int pkt_edit_host(const pkt_batch_t* b, const pkt_out_t* parsed, const pkt_edit_
     if (!dst || !parsed->status || !parsed->n_hdrs || !parsed->hdr_type || !parsed->hdr_off || !parsed->payload_off ||
         !parsed->payload_len)
         return PKT_ERR_INVALID_ARG;
-    if ((b->slab_len && !b->slab) || (b->offsets && !b->lens) || (!b->offsets && b->stride == 0)) return PKT_ERR_INVALID_ARG;
+    if (bad_batch(b)) return PKT_ERR_INVALID_ARG;
+    const BatchSrc src = batch_src(b);
     struct Ent {
         uint8_t type, konst;  // konst: the bytes are hdr_data[at ..], else the packet's [at ..]
         uint32_t at, size;
     };
     for (uint64_t i = 0; i < n; i++) {
-        const uint64_t off = b->offsets ? b->offsets[i] : i * b->stride;
-        const uint64_t left = off < b->slab_len ? b->slab_len - off : 0;
-        uint64_t l = b->lens ? b->lens[i] : b->stride;
-        l = l > left ? left : l;
-        const uint32_t len = l > 65535 ? 65535u : (uint32_t)l;
+        const uint64_t off = pkt_off(src, i);
+        const uint32_t len = pkt_len(src, i, off);
         const uint64_t o = dst_offsets ? dst_offsets[i] : i * slot;
         const uint64_t room = o >= dst_len ? 0 : (dst_len - o < slot ? dst_len - o : slot);
         // a slice of the packet, clamped to [0, len)

@@ -293,11 +293,11 @@ int pkt_parse_host(pkt_ctx_t* ctx, const pkt_batch_t* b, int entry, const pkt_ou
     if (entry < 0 || entry >= PKT_ENTRY_COUNT) return fail(ctx, PKT_ERR_INVALID_ARG, "bad entry");
     if (b->n == 0) return PKT_SUCCESS;
     if (!b->slab || b->slab_len == 0) return fail(ctx, PKT_ERR_INVALID_ARG, "null or empty slab");
-    if (b->offsets && !b->lens) return fail(ctx, PKT_ERR_INVALID_ARG, "offsets without lens");
-    if (!b->offsets && b->stride == 0) return fail(ctx, PKT_ERR_INVALID_ARG, "stride 0");
+    int rc = check_batch_index(ctx, b);
+    if (rc != PKT_SUCCESS) return rc;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
-    int rc = host_pipe_init(ctx);
+    rc = host_pipe_init(ctx);
     if (rc != PKT_SUCCESS) return rc;
     HostPipe& hp = ctx->hp;
     // Zero copy: when the slab, the index arrays and every requested column are pinned host memory

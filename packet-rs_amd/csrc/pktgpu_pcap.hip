@@ -157,13 +157,6 @@ __device__ __forceinline__ uint32_t lane_id() {
     return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 }
 
-// Order a wave's LDS writes before its other lanes' reads (no block barrier).
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ uint32_t ld32(const uint32_t* lw, uint32_t o) {
     // Little-endian u32 at any byte offset of the staged bytes (two dwords + v_alignbyte).
     return __builtin_amdgcn_alignbyte(lw[(o >> 2) + 1], lw[o >> 2], o & 3);
@@ -629,7 +622,7 @@ __global__ __launch_bounds__(256) void pcap_guess_kernel(const uint8_t* __restri
     // profiles/ab/r03i_pcap_uniform_walk.txt)
     uint16_t* dst = S.list + (uint64_t)k * kMaxRec;
     walk(lw, lbase, lst[w], base, entry, len, exit, cnt, err, rec);
-    wave_lds_sync();
+    wave_sync();
     const uint32_t nl = cnt + (err && cnt < kMaxRec ? 1u : 0u);  // + an overrunning record's start
     if (lane < nl) dst[lane] = (uint16_t)rec;
     for (uint32_t i = 64 + lane; i < nl; i += 64) dst[i] = lst[w][i];
@@ -803,9 +796,9 @@ __global__ __launch_bounds__(256) void pcap_scan_kernel(const uint8_t* __restric
         for (uint32_t i = w; i < nf; i += kWaves) {
             const uint32_t r = fq[i], kk = S.r0 + blk * kScanRegions + r;
             const uint64_t base = (uint64_t)kk * kRegion, e = fe[i];
-            wave_lds_sync();
+            wave_sync();
             if (e < base + kRegion) stage<kRegion, 64>(lds[w], buf, base, len, lane);
-            wave_lds_sync();
+            wave_sync();
             if (len - base <= 0x7FFFFFF0ull) {  // wave-uniform
                 // one lane walks (lane_walk2: the whole-wave walk below took ~9 us per fixed
                 // region, on the scan's critical path: profiles/pcap/r04q_stamps_guess_scan.txt)
@@ -813,7 +806,7 @@ __global__ __launch_bounds__(256) void pcap_scan_kernel(const uint8_t* __restric
                 uint32_t cw = 0;
                 if (lane == 0)
                     lane_walk2(reinterpret_cast<const uint32_t*>(lds[w]), base, lst[w], base, e, len, true, ex, cw);
-                wave_lds_sync();
+                wave_sync();
                 cw = (uint32_t)__shfl((int)cw, 0, 64);
                 ex = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(ex >> 32), 0, 64) << 32) |
                      (uint32_t)__shfl((int)(uint32_t)ex, 0, 64);
@@ -834,7 +827,7 @@ __global__ __launch_bounds__(256) void pcap_scan_kernel(const uint8_t* __restric
             uint64_t exit;
             uint32_t cnt, err, rec;
             walk(reinterpret_cast<const uint32_t*>(lds[w]), base, lst[w], base, e, len, exit, cnt, err, rec);
-            wave_lds_sync();
+            wave_sync();
             uint16_t* dst = S.list + (uint64_t)kk * kMaxRec;
             if (lane < cnt) dst[lane] = (uint16_t)rec;
             for (uint32_t j = 64 + lane; j < cnt; j += 64) dst[j] = lst[w][j];

@@ -36,26 +36,13 @@ constexpr uint32_t kPwSlots = 264;
 static_assert(kPwSlots >= kPwRec, "LDS slots per wave");
 
 struct WSrc {
-    const uint8_t* slab;
-    uint64_t slab_len;
-    const uint64_t* offsets;
-    const uint32_t* lens;
+    BatchSrc b;
     const uint8_t* select;
     const uint32_t* ts_sec;
     const uint32_t* ts_usec;
-    uint32_t stride, snaplen, tv_sec, tv_usec;
+    uint32_t snaplen, tv_sec, tv_usec;
     uint64_t n;  // < 2^32
 };
-
-__device__ __forceinline__ uint64_t w_off(const WSrc& a, uint64_t i) { return a.offsets ? a.offsets[i] : i * a.stride; }
-
-// pkt_batch_t's packet length: clamped to the slab end and to 65535
-__device__ __forceinline__ uint32_t w_len(const WSrc& a, uint64_t i, uint64_t off) {
-    uint32_t l = a.lens ? a.lens[i] : a.stride;
-    const uint64_t room = off < a.slab_len ? a.slab_len - off : 0;
-    l = l > room ? (uint32_t)room : l;
-    return l > 65535u ? 65535u : l;
-}
 
 __device__ __forceinline__ uint32_t w_incl(const WSrc& a, uint32_t len) {
     return a.snaplen && len > a.snaplen ? a.snaplen : len;
@@ -64,18 +51,13 @@ __device__ __forceinline__ uint32_t w_incl(const WSrc& a, uint32_t len) {
 // packet i's record bytes (low half) and record count (high half); 0 when not selected
 __device__ __forceinline__ uint64_t w_contrib(const WSrc& a, uint64_t i) {
     if (i >= a.n || (a.select && !a.select[i])) return 0;
-    return (uint64_t)(16u + w_incl(a, w_len(a, i, w_off(a, i)))) | 1ull << 32;
+    return (uint64_t)(16u + w_incl(a, pkt_len(a.b, i, pkt_off(a.b, i)))) | 1ull << 32;
 }
 
 // Exclusive prefix of v over the block's threads; total = the block's sum.  (s_w: one word per wave.)
 __device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* s_w, uint64_t& total) {
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint64_t x = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint64_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
+    const uint64_t x = wave_incl_scan(v, lane);
     if (lane == 63) s_w[wv] = x;
     __syncthreads();
     uint64_t base = 0;
@@ -193,39 +175,6 @@ __global__ __launch_bounds__(kPwBlock) void pw_emit_kernel(WSrc a, const uint64_
     }
 }
 
-struct U128 {
-    uint64_t lo, hi;
-};
-
-// v's bytes moved up by b (0..15) places, zeros coming in
-__device__ __forceinline__ U128 bytes_up(U128 v, uint32_t b) {
-    const uint32_t s = 8u * (b & 7u);
-    if (b >= 8) return U128{0, v.lo << s};
-    if (!s) return v;
-    return U128{v.lo << s, v.hi << s | v.lo >> (64u - s)};
-}
-
-// v's bytes moved down by b (0..15) places
-__device__ __forceinline__ U128 bytes_down(U128 v, uint32_t b) {
-    const uint32_t s = 8u * (b & 7u);
-    if (b >= 8) return U128{v.hi >> s, 0};
-    if (!s) return v;
-    return U128{v.lo >> s | v.hi << (64u - s), v.hi >> s};
-}
-
-// ones in bytes [0, b), b in 0..16
-__device__ __forceinline__ U128 bytes_below(uint32_t b) {
-    const uint64_t lo = b >= 8 ? ~0ull : (1ull << (8u * b)) - 1;
-    const uint64_t hi = b <= 8 ? 0ull : b >= 16 ? ~0ull : (1ull << (8u * (b - 8))) - 1;
-    return U128{lo, hi};
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(kPwBlock) void pw_copy_kernel(WSrc a, const uint64_t* __restrict__ tot, uint64_t dst_len,
                                                            const uint64_t* __restrict__ k_off,
                                                            const uint32_t* __restrict__ k_src,
@@ -263,8 +212,8 @@ __global__ __launch_bounds__(kPwBlock) void pw_copy_kernel(WSrc a, const uint64_
             const uint64_t i = k_src[k];
             if (h < we) {
                 in = true;
-                src = w_off(a, i);
-                const uint32_t orig = w_len(a, i, src);
+                src = pkt_off(a.b, i);
+                const uint32_t orig = pkt_len(a.b, i, src);
                 len = w_incl(a, orig) | orig << 16;
                 sec = a.ts_sec ? a.ts_sec[i] : a.tv_sec;
                 usec = a.ts_usec ? a.ts_usec[i] : a.tv_usec;
@@ -285,9 +234,9 @@ __global__ __launch_bounds__(kPwBlock) void pw_copy_kernel(WSrc a, const uint64_
         if (!((__ballot(in) >> 63) & 1ull)) break;  // a record past the window (or the last one) was seen
     }
     wave_sync();
-    const uint64_t last16 = a.slab_len ? ((a.slab_len + 15) & ~(uint64_t)15) - 16 : 0;
+    const uint64_t last16 = a.b.slab_len ? ((a.b.slab_len + 15) & ~(uint64_t)15) - 16 : 0;
     constexpr uint32_t kQ = kPwWin / 16 / 64;  // chunks per lane
-    U128 o[kQ];
+    Le128 o[kQ];
     uint4 v0[kQ], v1[kQ];
     uint32_t dsh[kQ], dlo[kQ], dhi[kQ];
     uint32_t run = 0;
@@ -301,15 +250,15 @@ __global__ __launch_bounds__(kPwBlock) void pw_copy_kernel(WSrc a, const uint64_
         const uint32_t P = run + below;  // the last record starting before the chunk
         const bool bit = (word >> lane) & 1ull;
         run += (uint32_t)__builtin_popcountll(word);
-        o[q] = U128{0, 0};
+        o[q] = Le128{0, 0};
         dlo[q] = dhi[q] = dsh[q] = 0;
         v0[q] = v1[q] = make_uint4(0, 0, 0, 0);
         if (ca >= total) continue;
-        if (ca < 24) o[q] = ca == 0 ? U128{0x00040002A1B2C3D4ull, 0} : U128{0x000000010000FFFFull, 0};
+        if (ca < 24) o[q] = ca == 0 ? Le128{0x00040002A1B2C3D4ull, 0} : Le128{0x000000010000FFFFull, 0};
         const int32_t relP = s_rel[wv][P] - (int32_t)(16u * g);  // its header's start, from the chunk's
         const uint32_t lenP = s_len[wv][P], inclP = lenP & 0xFFFFu;
         if (relP > -16) {  // the tail of its header
-            const U128 h = bytes_down(U128{(uint64_t)s_sec[wv][P] | (uint64_t)s_usec[wv][P] << 32,
+            const Le128 h = bytes_down(Le128{(uint64_t)s_sec[wv][P] | (uint64_t)s_usec[wv][P] << 32,
                                            (uint64_t)inclP | (uint64_t)(lenP >> 16) << 32},
                                       (uint32_t)(-relP));
             o[q].lo |= h.lo, o[q].hi |= h.hi;
@@ -317,7 +266,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_copy_kernel(WSrc a, const uint64_
         if (bit) {  // the head of the next record's header
             const uint32_t lenQ = s_len[wv][P + 1];
             const int32_t relQ = s_rel[wv][P + 1] - (int32_t)(16u * g);
-            const U128 h = bytes_up(U128{(uint64_t)s_sec[wv][P + 1] | (uint64_t)s_usec[wv][P + 1] << 32,
+            const Le128 h = bytes_up(Le128{(uint64_t)s_sec[wv][P + 1] | (uint64_t)s_usec[wv][P + 1] << 32,
                                          (uint64_t)(lenQ & 0xFFFFu) | (uint64_t)(lenQ >> 16) << 32},
                                     (uint32_t)relQ & 15u);
             o[q].lo |= h.lo, o[q].hi |= h.hi;
@@ -333,8 +282,8 @@ __global__ __launch_bounds__(kPwBlock) void pw_copy_kernel(WSrc a, const uint64_
             const int64_t A = B & ~(int64_t)15;
             dsh[q] = (uint32_t)(B - A);
             const int64_t a0 = A < 0 ? 0 : A, a1 = A + 16;
-            v0[q] = *reinterpret_cast<const uint4*>(a.slab + ((uint64_t)a0 > last16 ? last16 : (uint64_t)a0));
-            v1[q] = *reinterpret_cast<const uint4*>(a.slab + ((uint64_t)a1 > last16 ? last16 : (uint64_t)a1));
+            v0[q] = *reinterpret_cast<const uint4*>(a.b.slab + ((uint64_t)a0 > last16 ? last16 : (uint64_t)a0));
+            v1[q] = *reinterpret_cast<const uint4*>(a.b.slab + ((uint64_t)a1 > last16 ? last16 : (uint64_t)a1));
         }
     }
 #pragma unroll
@@ -348,7 +297,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_copy_kernel(WSrc a, const uint64_
             const uint64_t y0 = up ? x1 : x0, y1 = up ? x2 : x1, y2 = up ? x3 : x2;
             const uint32_t s = 8u * (dsh[q] & 7u);
             const uint64_t lo = s ? y0 >> s | y1 << (64u - s) : y0, hi = s ? y1 >> s | y2 << (64u - s) : y1;
-            const U128 m1 = bytes_below(dhi[q]), m0 = bytes_below(dlo[q]);
+            const Le128 m1 = bytes_below(dhi[q]), m0 = bytes_below(dlo[q]);
             o[q].lo |= lo & m1.lo & ~m0.lo;
             o[q].hi |= hi & m1.hi & ~m0.hi;
         }
@@ -382,10 +331,9 @@ int pw_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const uint8_t* select, uint32
     if (dst_len && !dst) return fail(ctx, PKT_ERR_INVALID_ARG, "null dst");
     if ((uintptr_t)dst & 15) return fail(ctx, PKT_ERR_INVALID_ARG, "dst not 16-byte aligned");
     if (b->n) {
-        if (b->slab_len && !b->slab) return fail(ctx, PKT_ERR_INVALID_ARG, "null slab");
-        if ((uintptr_t)b->slab & 15) return fail(ctx, PKT_ERR_INVALID_ARG, "slab not 16-byte aligned");
-        if (b->offsets && !b->lens) return fail(ctx, PKT_ERR_INVALID_ARG, "offsets without lens");
-        if (!b->offsets && b->stride == 0) return fail(ctx, PKT_ERR_INVALID_ARG, "stride 0");
+        int rc = check_batch_slab16(ctx, b);
+        if (rc == PKT_SUCCESS) rc = check_batch_index(ctx, b);
+        if (rc != PKT_SUCCESS) return rc;
     }
     PcapWriteScratch& pw = ctx->pw;
     if (pw.pending)
@@ -421,14 +369,10 @@ int pw_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const uint8_t* select, uint32
     uint64_t* k_off = rec_offsets ? rec_offsets : reinterpret_cast<uint64_t*>(p + o_koff);
     uint32_t* k_src = src_index ? src_index : reinterpret_cast<uint32_t*>(p + o_ksrc);
     WSrc a;
-    a.slab = b->slab;
-    a.slab_len = b->slab_len;
-    a.offsets = b->offsets;
-    a.lens = b->lens;
+    a.b = batch_src(b);
     a.select = select;
     a.ts_sec = ts_sec;
     a.ts_usec = ts_usec;
-    a.stride = b->stride;
     a.snaplen = snaplen;
     a.tv_sec = tv_sec;
     a.tv_usec = tv_usec;

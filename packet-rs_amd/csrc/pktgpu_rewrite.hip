@@ -42,27 +42,18 @@ using namespace pktgpu;
 
 namespace {
 
-__constant__ uint8_t kHdrSize[PKT_HDR_COUNT] = {0, 14, 4, 20, 40, 4, 20, 8, 28, 8, 14, 3, 5, 4, 4, 4, 4, 8, 12, 8, 35, 4};
+__constant__ uint8_t kHdrSize[PKT_HDR_COUNT] = PKT_HDR_SIZE_LIST;
 
 constexpr uint32_t kRwBlock = 256;
 constexpr int kMaxSpecs = 32;  // specs per launch (extract / set_fields)
 static_assert(kRwBlock >= (uint32_t)kMaxSpecs, "one thread copies each spec into the LDS spec table");
 
-struct BatchRef {
-    const uint8_t* slab;
-    uint64_t slab_len;
-    const uint64_t* offsets;
-    const uint32_t* lens;
-    uint32_t stride;
+struct BatchRef : BatchSrc {
     uint64_t n;
     const uint8_t* n_hdrs;
     const uint8_t* hdr_type;   // [PKT_MAX_HDRS][n]
     const uint16_t* hdr_off;   // [PKT_MAX_HDRS][n]
 };
-
-__device__ __forceinline__ uint64_t pkt_off(const BatchRef& b, uint64_t i) {
-    return b.offsets ? b.offsets[i] : i * (uint64_t)b.stride;
-}
 
 // aligned dword of the slab containing byte a, clamped to the readable end (round_up(len, 16))
 __device__ __forceinline__ uint32_t slab_dw(const BatchRef& b, uint64_t a) {
@@ -82,25 +73,10 @@ struct ChainLds {
     uint16_t off[kChainLds][kRwBlock];
 };
 
-// Stage packet i's first slots in LDS: chain_load issues n_hdrs and the first 4 slot rows
-// unconditionally (the columns are [PKT_MAX_HDRS][n], so rows past n_hdrs are readable; their
-// bytes are never used), so that they are in flight together with the caller's other loads: one
-// memory round trip for the common chains instead of one per slot.  chain_store writes them and
-// loads any deeper slots; returns n_hdrs (clamped to PKT_MAX_HDRS).
-static_assert(PKT_MAX_HDRS >= 4 && kChainLds >= 4, "first 4 slot rows staged unconditionally");
-struct ChainPre {
-    uint32_t nh, ty[4], of[4];
-};
-__device__ __forceinline__ ChainPre chain_load(const BatchRef& b, uint64_t i) {
-    ChainPre c;
-    c.nh = b.n_hdrs[i];
-#pragma unroll
-    for (uint32_t j = 0; j < 4; j++) {
-        c.ty[j] = b.hdr_type[(uint64_t)j * b.n + i];
-        c.of[j] = b.hdr_off[(uint64_t)j * b.n + i];
-    }
-    return c;
-}
+// Stage packet i's first slots in LDS: chain_load (pktgpu_batch.hpp) issues n_hdrs and the first 4
+// slot rows together with the caller's other loads; chain_store writes them and loads any deeper
+// slots; returns n_hdrs (clamped to PKT_MAX_HDRS).
+static_assert(kChainLds >= 4, "first 4 slot rows staged unconditionally");
 __device__ __forceinline__ uint32_t chain_store(const BatchRef& b, uint64_t i, uint32_t t, ChainLds& L, const ChainPre& c) {
     const uint32_t nh = c.nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : c.nh;
 #pragma unroll
@@ -511,7 +487,9 @@ __global__ __launch_bounds__(kRwBlock) void to_vec_kernel(TParams p) {
     __shared__ uint32_t s_clen[kRwBlock / 64][64], s_cpre[kRwBlock / 64][64];
     const bool flat = ok && ident && len > 0;
     const uint32_t ch = flat ? (uint32_t)(((dst & 15) + len + 15) >> 4) : 0u;
-    uint32_t incl = ch;  // inclusive scan over the wave
+    // inclusive scan over the wave: wave_incl_scan's loop, written out (called, it moves one scalar
+    // instruction of this kernel's schedule, and the kernel's listing is kept as it was measured)
+    uint32_t incl = ch;
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {
         const uint32_t t = (uint32_t)__shfl_up((int)incl, (unsigned)m, 64);
@@ -523,9 +501,7 @@ __global__ __launch_bounds__(kRwBlock) void to_vec_kernel(TParams p) {
     s_src[w][lane] = src;
     s_dst[w][lane] = dst;
     s_len[w][lane] = len;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     const uint64_t last16 = ((p.b.slab_len + 15) & ~(uint64_t)15) - 16;
     // Chunk -> packet without a search: bit g of the wave's start map is set iff a packet's first
     // chunk is g, and the flat packets' (src, dst, len, pre) are stored compacted by rank, so chunk
@@ -544,16 +520,12 @@ __global__ __launch_bounds__(kRwBlock) void to_vec_kernel(TParams p) {
             s_clen[w][rank] = len;
             s_cpre[w][rank] = incl - ch;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         if (ch) {
             const uint32_t g0 = incl - ch;
             atomicOr(reinterpret_cast<uint32_t*>(s_map[w]) + (g0 >> 5), 1u << (g0 & 31u));
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
     }
     uint32_t run = 0;  // starts in the rounds before the one being located (uniform)
     // A wave whose 64 outputs lie back to back in the destination (a fixed-stride slab of whole
@@ -700,17 +672,13 @@ __global__ __launch_bounds__(kRwBlock) void tv_window_kernel(TParams p, const ui
         if (lane < kTvWinWords) s_map[wv][lane] = 0;
         s_o[wv][lane] = o;
         s_l[wv][lane] = len | md << 30;  // len <= 2 * 65535
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         const bool st = sin && o < we;  // starts at chunk (o - wa) / 16 of this window
         if (st) {
             const uint32_t g = (uint32_t)((o - wa) >> 4);
             atomicOr(reinterpret_cast<uint32_t*>(s_map[wv]) + (g >> 5), 1u << (g & 31u));
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         // chunk g's record: lane (starts at or below g) - s0, s0 = 1 when the batch's first record
         // starts in the window (chunks before it are not the batch's), else it began before
         const uint32_t s0 = (uint32_t)(__ballot(st) & 1ull);
@@ -768,9 +736,7 @@ __global__ __launch_bounds__(kRwBlock) void tv_window_kernel(TParams p, const ui
     if (i0 >= p.b.n) return;
     for (bool more = batch(i0); more && i0 + 64 < p.b.n; more = batch(i0)) {  // uniform
         i0 += 64;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
     }
 }
 
@@ -969,9 +935,7 @@ __global__ __launch_bounds__(kRwBlock) void set_fields_kernel(SParams p) {
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     // write back the dirty chunks, the packet's own bytes only, with the pairs of the loads
 #pragma unroll
     for (uint32_t k = 0; k < (uint32_t)NCH; k++) {
@@ -1056,13 +1020,9 @@ bool narrow_slots(const pkt_batch_t* b) { return !b->offsets && b->stride <= 64 
 int batch_ref(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, BatchRef& r) {
     if (!b->slab || !chain || !chain->n_hdrs || !chain->hdr_type || !chain->hdr_off)
         return fail(ctx, PKT_ERR_INVALID_ARG, "null slab/chain column");
-    if (b->offsets && !b->lens) return fail(ctx, PKT_ERR_INVALID_ARG, "offsets without lens");
-    if (!b->offsets && b->stride == 0) return fail(ctx, PKT_ERR_INVALID_ARG, "stride 0");
-    r.slab = b->slab;
-    r.slab_len = b->slab_len;
-    r.offsets = b->offsets;
-    r.lens = b->lens;
-    r.stride = b->stride;
+    const int rc = check_batch_index(ctx, b);
+    if (rc != PKT_SUCCESS) return rc;
+    static_cast<BatchSrc&>(r) = batch_src(b);
     r.n = b->n;
     r.n_hdrs = chain->n_hdrs;
     r.hdr_type = chain->hdr_type;
