@@ -680,6 +680,65 @@ int pkt_edit_host(const pkt_batch_t *batch, const pkt_out_t *parsed, const pkt_e
                   uint64_t dst_len, const uint64_t *dst_offsets, uint32_t slot, uint32_t *out_len,
                   uint8_t *edit_status, const pkt_out_t *out_chain);
 
+/* ---- L4 checksums of a batch ----
+ * The TCP / UDP / ICMP checksum of every packet, verified and optionally stored: the sibling of
+ * pkt_ipv4_checksum_batch that the reference announces and never builds (`_tcp_checksum`, `_udp_checksum`:
+ * utils.rs:156, 213, 261, 439, 480, 520, 565 take the flag and ignore it; the v6 builders store a literal
+ * 0xffff, utils.rs:461, 589).  It is the one rewrite-side operation that reads every payload byte.
+ *  - batch / chain: any pkt_batch_t under its usual slab rules, with the chain columns of a parse of it, or
+ *    pkt_edit_batch's out_chain.  n_hdrs is taken as min(n_hdrs, PKT_MAX_HDRS).
+ *  - The L4 header is the `which`-th list entry whose type is TCP, UDP or ICMP, the three counted together
+ *    in list order from 0; PKT_L4_LAST takes the last such entry.  (A VXLAN packet has its outer UDP at 0
+ *    and its inner TCP at 1, which is also LAST.)  `which` in 16..0xFE is PKT_ERR_INVALID_ARG.  A chain
+ *    without that entry (n_hdrs == 0 included) is PKT_L4_ABSENT.
+ *  - The IP header is the list entry immediately before the L4 header, where the walk always puts it
+ *    (fast.rs:84-113).  Any other type there, or an L4 header at slot 0, is PKT_L4_NO_IP.
+ *  - The segment is the packet-relative span [s, e).  s = the chain's hdr_off of the L4 header (the
+ *    reference places L4 at IP + 20 whatever ihl says; this call follows the chain).  e = hdr_off(IP) +
+ *    total_len for IPv4, hdr_off(IP) + 40 + payload_len for IPv6: the IP header's length, not the packet's
+ *    end (a 60-byte padded frame carries bytes past e that are not summed).  PKT_L4_SPAN: the IP header's
+ *    20 / 40 bytes do not lie inside the packet (its length under the pkt_batch_t clamp rules), e exceeds
+ *    that length, or e < s + pkt_hdr_size(L4 type).  PKT_L4_FRAGMENT: IPv4 with (bytes 6..7 & 0x3FFF) != 0,
+ *    decided after the IP header is known to be inside the packet and before e is examined.
+ *  - The sum is RFC 1071's: the one's-complement sum of the 16-bit big-endian words of the pseudo-header
+ *    and the segment, the segment's checksum field (TCP bytes 16-17, UDP 6-7, ICMP 2-3) taken as zero and
+ *    an odd last byte padded with zero.  It is the correct end-around-carry fold, not Packet::ipv4_checksum's
+ *    (Q1): this value has to interoperate with real stacks and the reference defines none.  IPv4
+ *    pseudo-header: src, dst, 0, proto, e - s as u16.  IPv6: src, dst, e - s as u32, 0, 0, 0, next.  proto /
+ *    next comes from the L4 type: TCP 6, UDP 17, ICMP under IPv6 58; ICMP under IPv4 has no pseudo-header.
+ *    calc = ~fold(sum); for UDP a calc of 0 becomes 0xFFFF.
+ *  - calc / stored / l4_status: device [n], each may be NULL.  calc = the value that belongs in the field,
+ *    stored = the field as read, before any update.  l4_status: UDP over IPv4 with stored == 0 is
+ *    PKT_L4_UNCHECKED, UDP over IPv6 with stored == 0 is PKT_L4_BAD, otherwise PKT_L4_OK or PKT_L4_BAD by
+ *    the rule at the enum.  For ABSENT, NO_IP, SPAN and FRAGMENT calc = stored = 0 and the packet is never
+ *    written.
+ *  - PKT_L4_UPDATE: the slab must be writable and the packets must not overlap, as for pkt_set_fields.  For
+ *    a packet with status OK, BAD or UNCHECKED exactly the two checksum bytes are stored, big-endian (with
+ *    PKT_L4_KEEP_ZERO_UDP an UNCHECKED packet is not stored); no other byte of the slab is written, not
+ *    even with its own value.  The status still describes the field as it was read.
+ *  - PKT_ERR_INVALID_ARG, before any launch: the usual batch and slab refusals, a NULL chain (with n > 0, a
+ *    NULL chain column), n >= 2^32, unknown flag bits, KEEP_ZERO_UDP without UPDATE, a bad `which`.  n == 0
+ *    succeeds and launches nothing.
+ * Asynchronous on `stream`, like pkt_edit_batch: no host wait, no summary and no ctx state.
+ * pkt_l4_checksum_host is the same operation on HOST pointers and needs no device or ctx. */
+typedef enum pkt_l4_status {
+    PKT_L4_OK        = 0, /* stored == calc (or stored 0xFFFF with calc 0: the two encodings of zero) */
+    PKT_L4_BAD       = 1,
+    PKT_L4_UNCHECKED = 2, /* UDP over IPv4 with a stored checksum of 0 (RFC 768: none sent) */
+    PKT_L4_ABSENT    = 3, /* the chain has no such L4 header (n_hdrs == 0 included) */
+    PKT_L4_NO_IP     = 4, /* the list entry just before the L4 header is neither IPv4 nor IPv6 */
+    PKT_L4_SPAN      = 5, /* the IP length puts the segment's end past the packet, or before the L4 header's end */
+    PKT_L4_FRAGMENT  = 6  /* IPv4 with MF set or a non-zero fragment offset */
+} pkt_l4_status_t;
+#define PKT_L4_LAST            0xFFu  /* which: the last TCP/UDP/ICMP header of the list */
+#define PKT_L4_UPDATE          1u     /* flags: store calc into the packet */
+#define PKT_L4_KEEP_ZERO_UDP   2u     /* flags: with UPDATE, leave an UNCHECKED packet's 0 alone */
+int pkt_l4_checksum_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain,
+                          uint32_t which, uint32_t flags, uint16_t *calc, uint16_t *stored,
+                          uint8_t *l4_status, void *stream);
+int pkt_l4_checksum_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which,
+                         uint32_t flags, uint16_t *calc, uint16_t *stored, uint8_t *l4_status);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -353,6 +353,85 @@ int pkt_edit_host(const pkt_batch_t* b, const pkt_out_t* parsed, const pkt_edit_
     return PKT_SUCCESS;
 }
 
+// pkt_l4_checksum_batch on host pointers (the CPU model of pktgpu_l4csum.hip): the RFC 1071 checksum of
+// every packet's TCP / UDP / ICMP segment with its pseudo-header, word by word.
+int pkt_l4_checksum_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which, uint32_t flags, uint16_t* calc,
+                         uint16_t* stored, uint8_t* l4_status) {
+    if (!b || !chain) return PKT_ERR_INVALID_ARG;
+    if (b->n >= (1ull << 32) || (flags & ~(PKT_L4_UPDATE | PKT_L4_KEEP_ZERO_UDP))) return PKT_ERR_INVALID_ARG;
+    if ((flags & PKT_L4_KEEP_ZERO_UDP) && !(flags & PKT_L4_UPDATE)) return PKT_ERR_INVALID_ARG;
+    if (which >= PKT_MAX_HDRS && which != PKT_L4_LAST) return PKT_ERR_INVALID_ARG;
+    const uint64_t n = b->n;
+    if (n == 0) return PKT_SUCCESS;
+    if (bad_batch(b) || !chain->n_hdrs || !chain->hdr_type || !chain->hdr_off) return PKT_ERR_INVALID_ARG;
+    const BatchSrc src = batch_src(b);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t off = pkt_off(src, i);
+        const uint32_t len = pkt_len(src, i, off);
+        uint32_t nh = chain->n_hdrs[i], seen = 0, slot = PKT_MAX_HDRS;
+        nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+        for (uint32_t j = 0; j < nh; j++) {
+            const uint8_t t = chain->hdr_type[j * n + i];
+            if (t != PKT_HDR_TCP && t != PKT_HDR_UDP && t != PKT_HDR_ICMP) continue;
+            if (which == PKT_L4_LAST || seen == which) slot = j;
+            seen++;
+        }
+        uint32_t st = PKT_L4_ABSENT, c = 0, sv = 0, field = 0;
+        if (slot < PKT_MAX_HDRS) {
+            const uint8_t t = chain->hdr_type[slot * n + i], ipt = slot ? chain->hdr_type[(slot - 1) * n + i] : 0;
+            const uint32_t s = chain->hdr_off[slot * n + i], ip = slot ? chain->hdr_off[(slot - 1) * n + i] : 0u;
+            const bool v4 = ipt == PKT_HDR_IPV4;
+            const uint8_t* p = b->slab + off;
+            if (!v4 && ipt != PKT_HDR_IPV6) {
+                st = PKT_L4_NO_IP;
+            } else if (ip + (v4 ? 20u : 40u) > len) {
+                st = PKT_L4_SPAN;
+            } else if (v4 && ((((uint32_t)p[ip + 6] << 8) | p[ip + 7]) & 0x3FFFu)) {
+                st = PKT_L4_FRAGMENT;
+            } else {
+                const uint32_t e = v4 ? ip + (((uint32_t)p[ip + 2] << 8) | p[ip + 3])
+                                      : ip + 40u + (((uint32_t)p[ip + 4] << 8) | p[ip + 5]);
+                if (e > len || e < s + kHdrs[t].size) {
+                    st = PKT_L4_SPAN;
+                } else {
+                    const uint32_t seg = e - s;
+                    field = s + (t == PKT_HDR_TCP ? 16u : t == PKT_HDR_UDP ? 6u : 2u);
+                    const uint32_t proto = t == PKT_HDR_TCP ? 6u : t == PKT_HDR_UDP ? 17u : 58u;
+                    uint64_t sum = 0;
+                    if (v4 && t != PKT_HDR_ICMP) {
+                        for (uint32_t k = 12; k < 20; k += 2) sum += ((uint32_t)p[ip + k] << 8) | p[ip + k + 1];
+                        sum += proto + seg;
+                    } else if (!v4) {
+                        for (uint32_t k = 8; k < 40; k += 2) sum += ((uint32_t)p[ip + k] << 8) | p[ip + k + 1];
+                        sum += proto + seg;  // seg < 2^16: the length's upper word is 0
+                    }
+                    for (uint32_t k = s; k < e; k += 2) {
+                        if (k == field) continue;
+                        sum += ((uint32_t)p[k] << 8) | (k + 1 < e ? p[k + 1] : 0u);
+                    }
+                    while (sum >> 16) sum = (sum & 0xFFFFu) + (sum >> 16);
+                    c = (uint32_t)~sum & 0xFFFFu;
+                    if (t == PKT_HDR_UDP && c == 0) c = 0xFFFFu;
+                    sv = ((uint32_t)p[field] << 8) | p[field + 1];
+                    if (t == PKT_HDR_UDP && sv == 0)
+                        st = v4 ? PKT_L4_UNCHECKED : PKT_L4_BAD;
+                    else
+                        st = sv == c || (sv == 0xFFFFu && c == 0) ? PKT_L4_OK : PKT_L4_BAD;
+                    if ((flags & PKT_L4_UPDATE) && !(st == PKT_L4_UNCHECKED && (flags & PKT_L4_KEEP_ZERO_UDP))) {
+                        uint8_t* w = const_cast<uint8_t*>(p);
+                        w[field] = (uint8_t)(c >> 8);
+                        w[field + 1] = (uint8_t)c;
+                    }
+                }
+            }
+        }
+        if (calc) calc[i] = (uint16_t)c;
+        if (stored) stored[i] = (uint16_t)sv;
+        if (l4_status) l4_status[i] = (uint8_t)st;
+    }
+    return PKT_SUCCESS;
+}
+
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,
 // packet.rs:724-731: insert / set_payload).
 int pkt_view(const pkt_out_t* out, uint64_t n, uint64_t i, uint8_t types[PKT_MAX_HDRS], uint16_t offs[PKT_MAX_HDRS],

@@ -631,6 +631,35 @@ class Parser:
         self._check(self._L.pkt_edit_batch(self._ctx, *args, self._stream(stream)), "pkt_edit_batch")
         return out
 
+    def _l4_args(self, slab, chain, which=0, update=False, keep_zero_udp=False, stride=None, n=None, offsets=None,
+                 lens=None, outputs=(True, True, True)):
+        """The marshalled arguments of pkt_l4_checksum_batch (after ctx, before stream); `outputs`: whether
+        calc, stored and status are asked for."""
+        torch = _torch()
+        b = self._batch(slab, n, stride, offsets, lens)
+        ch = self._chain(chain)
+        flags = (schema.L4_UPDATE if update else 0) | (schema.L4_KEEP_ZERO_UDP if keep_zero_udp else 0)
+        dts = (torch.uint16, torch.uint16, torch.uint8)
+        out = tuple(torch.empty(b.n, dtype=dt, device=self.torch_device) if want else None
+                    for dt, want in zip(dts, outputs))
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        args = (ctypes.byref(b), ctypes.byref(ch), int(which), flags, ptr(out[0]), ptr(out[1]), ptr(out[2]))
+        return args, out, (b, ch)
+
+    def l4_checksum(self, slab, chain, which=0, update=False, keep_zero_udp=False, stride=None, n=None, offsets=None,
+                    lens=None, stream=None):
+        """pkt_l4_checksum_batch: the RFC 1071 checksum of every packet's TCP / UDP / ICMP segment with its
+        pseudo-header -> {"calc": uint16, "stored": uint16, "status": uint8} (pktgpu.L4_OK / _BAD /
+        _UNCHECKED / _ABSENT / _NO_IP / _SPAN / _FRAGMENT; names in schema.L4_STATUS).  `chain`: the chain
+        columns of a parse of the batch, or edit's out chain.  `which`: the k-th TCP / UDP / ICMP header of
+        the list, counted together from 0, or pktgpu.L4_LAST.  update=True stores calc into the packets
+        (exactly the two checksum bytes of each summed packet; keep_zero_udp=True leaves a UDP/IPv4
+        checksum of 0 alone); the status still describes the field as it was read.  Asynchronous on
+        `stream`."""
+        args, out, keep = self._l4_args(slab, chain, which, update, keep_zero_udp, stride, n, offsets, lens)
+        self._check(self._L.pkt_l4_checksum_batch(self._ctx, *args, self._stream(stream)), "pkt_l4_checksum_batch")
+        return {"calc": out[0], "stored": out[1], "status": out[2]}
+
     def pcap_index_device_timed(self, buf, offsets, lens, stream=None):
         """pkt_pcap_index_device_timed into the caller's device `offsets` / `lens` (cap = their
         length): (record count, [guess, scan, emit] kernel ms from HIP events between them)."""
@@ -862,6 +891,31 @@ def edit(slab, parsed, ops, stride=None, n=None, offsets=None, lens=None, select
     if rc != 0:
         raise ValueError(f"pkt_edit_host failed ({rc})")
     return dst, out_len, status, chain
+
+
+L4_OK, L4_BAD, L4_UNCHECKED, L4_ABSENT, L4_NO_IP, L4_SPAN, L4_FRAGMENT = range(7)
+L4_LAST = schema.L4_LAST
+
+
+def l4_checksum(slab, chain, which=0, update=False, keep_zero_udp=False, stride=None, n=None, offsets=None, lens=None):
+    """pkt_l4_checksum_host over numpy arrays (no device): Parser.l4_checksum's arguments with numpy arrays
+    -> {"calc", "stored", "status"}.  update=True writes into `slab` itself, which must then be a
+    writable C-contiguous uint8 array."""
+    from . import _lib
+    L = _lib.load()
+    if update:
+        assert isinstance(slab, np.ndarray) and slab.dtype == np.uint8 and slab.flags.c_contiguous and slab.flags.writeable
+    b, keep = _host_batch(_lib, dict(slab=slab, stride=stride, n=n, offsets=offsets, lens=lens))
+    cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+            np.ascontiguousarray(chain["hdr_off"], np.uint16))
+    ch = _lib.PktChain(*[c.ctypes.data for c in cols])
+    flags = (schema.L4_UPDATE if update else 0) | (schema.L4_KEEP_ZERO_UDP if keep_zero_udp else 0)
+    calc, stored, status = np.zeros(b.n, np.uint16), np.zeros(b.n, np.uint16), np.zeros(b.n, np.uint8)
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    rc = L.pkt_l4_checksum_host(ctypes.byref(b), ctypes.byref(ch), int(which), flags, ptr(calc), ptr(stored), ptr(status))
+    if rc != 0:
+        raise ValueError(f"pkt_l4_checksum_host failed ({rc})")
+    return {"calc": calc, "stored": stored, "status": status}
 
 
 # ----------------------------------------------------------------- PacketSlice-style host views

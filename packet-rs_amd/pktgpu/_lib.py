@@ -155,6 +155,10 @@ SIGNATURES = {
     "pkt_edit_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktOut), ctypes.POINTER(PktEditOp),
                                      ctypes.c_uint32, _P, ctypes.c_uint32, _P, _P, ctypes.c_uint64, _P, ctypes.c_uint32,
                                      _P, _P, ctypes.POINTER(PktOut)]),
+    "pkt_l4_checksum_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                             ctypes.c_uint32, _P, _P, _P, _P]),
+    "pkt_l4_checksum_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                            ctypes.c_uint32, _P, _P, _P]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),

@@ -14,6 +14,12 @@ ABI_VERSION = 5
 OK, TRUNCATED, DEPTH_LIMIT = 0, 1, 2
 STATUS_NAMES = ["OK", "TRUNCATED", "DEPTH_LIMIT"]
 
+# pkt_l4_status_t (pkt_l4_checksum_batch)
+L4_OK, L4_BAD, L4_UNCHECKED, L4_ABSENT, L4_NO_IP, L4_SPAN, L4_FRAGMENT = range(7)
+L4_STATUS = ["OK", "BAD", "UNCHECKED", "ABSENT", "NO_IP", "SPAN", "FRAGMENT"]
+L4_LAST = 0xFF
+L4_UPDATE, L4_KEEP_ZERO_UDP = 1, 2
+
 # pkt_hdr_type_t -> Header::name() of the reference (headers.rs:529-827)
 HDR_NAMES = [
     "", "Ether", "Vlan", "IPv4", "IPv6", "ICMP", "TCP", "UDP", "ARP", "Vxlan", "Dot3",

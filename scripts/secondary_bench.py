@@ -23,6 +23,9 @@
                  _bytes_only, with the status, length and chain outputs NULL), edit_encap_c2 (VXLAN encap, 64 ->
                  114 bytes in 128-byte slots), edit_decap_c2 (the decap of that output through its out chain) and
                  edit_vlan_strip_c3 (the first tag of C3 removed, 128-byte slots to 128-byte slots)
+  l4             pkt_l4_checksum_batch (the TCP / UDP / ICMP checksum with its pseudo-header, RFC 1071), four lines:
+                 l4_verify_c2 / l4_update_c2 (the C2 slab at fixed stride, which = 0) and l4_verify_c4 / l4_update_c4
+                 (an indexed batch over a C4 capture in place, which = PKT_L4_LAST), read-only and with PKT_L4_UPDATE
   extract_c2     every field of Ether/IPv4/UDP (19 specs, one launch) over C2 (headers.rs:195-201)
   setfields_c2   4 setters + the IPv4 checksum refresh, in place over C2 (headers.rs:315-324)
 
@@ -434,6 +437,71 @@ def main():
                 # written: result, matching, first_diff
                 line(f"compare_{tag}{sfx}", n, ms, 128 + idx_b + (1 + 3 * 3 if ignore else 0), 9, cpu, extra)
         del caps, copies, rewritten
+    if want("l4"):
+        T4, T6 = schema.HDR_ID["IPv4"], schema.HDR_ID["IPv6"]
+        L4T = [schema.HDR_ID[k] for k in ("ICMP", "TCP", "UDP")]
+
+        def l4_lines(tag, bufs, dkw, hslab, hkw, which, chs, idx_b):
+            """l4_verify_<tag> and l4_update_<tag>: kernel time of pkt_l4_checksum_batch over a ring of copies of
+            the batch, its arguments marshalled once per copy; parity of the three outputs and of the updated
+            slab against pkt_l4_checksum_host over the whole batch."""
+            hch = {k: chs[0][k].cpu().numpy() for k in ("n_hdrs", "hdr_type", "hdr_off")}
+            twin = pktgpu.l4_checksum(hslab, hch, which, **hkw)
+            summed = twin["status"] <= schema.L4_UNCHECKED
+            # the bytes a summed packet's checksum needs: its segment, the IP header's length, fragment and
+            # address bytes, the chain (n_hdrs and its slots), the index when there is one
+            isl4 = np.isin(hch["hdr_type"], L4T) & (np.arange(schema.MAX_HDRS)[:, None] < hch["n_hdrs"][None, :])
+            pick = np.where(isl4.any(0), schema.MAX_HDRS - 1 - np.argmax(isl4[::-1], axis=0), 0) if which == schema.L4_LAST \
+                else np.argmax(isl4, axis=0)
+            cols = np.arange(hch["n_hdrs"].size)
+            s_off = hch["hdr_off"][pick, cols].astype(np.int64)
+            ipt = hch["hdr_type"][np.maximum(pick, 1) - 1, cols]
+            plen = hkw["lens"].astype(np.int64) if hkw.get("lens") is not None else np.full(cols.size, hkw["stride"], np.int64)
+            # (the segment's end taken as the packet's end, as it is for all but a few C4 templates)
+            seg = np.where(summed, plen - s_off + np.where(ipt == T4, 12, np.where(ipt == T6, 34, 0)), 0)
+            read_b = round(float(seg.mean()) + 1 + 3 * float(np.minimum(hch["n_hdrs"], schema.MAX_HDRS).mean()) + idx_b, 1)
+            sample = min(n, 1 << 18)
+            if hkw.get("offsets") is not None:
+                ckw = dict(offsets=hkw["offsets"][:sample], lens=hkw["lens"][:sample])
+            else:
+                ckw = dict(stride=hkw["stride"], n=sample)
+            cch = {k: np.ascontiguousarray(v[..., :sample]) for k, v in hch.items()}
+            r, t = timed(lambda: pktgpu.l4_checksum(hslab, cch, which, **ckw), args.cpu_budget)
+            cpu = {"value": round(r * sample / t / 1e9, 6), "unit": "Gpkt/s", "cores": 1, "kind": "port",
+                   "sample": f"{r} x {sample} packets of pkt_l4_checksum_host (the CPU model: a big-endian word loop "
+                             "over pseudo-header and segment), 1 thread"}
+            for upd in (False, True):
+                work = [b_.clone() for b_ in bufs] if upd else bufs
+                prep = [P._l4_args(w_, c_, which, upd, **bkw)
+                        for w_, c_, bkw in zip(work, chs, dkw)]
+                s = P._stream(None)
+
+                def launch(k_):
+                    assert P._L.pkt_l4_checksum_batch(P._ctx, *prep[k_ % len(prep)][0], s) == 0
+                ms = min(event_ms(launch, it) for _ in range(3))
+                got = {k: v.cpu().numpy() for k, v in zip(("calc", "stored", "status"), prep[0][1])}
+                if upd:  # after the first update the field holds calc: the outputs of the later launches
+                    ok = np.array_equal(got["calc"], twin["calc"]) and np.array_equal(got["stored"][summed], twin["calc"][summed])
+                    hs = hslab.copy()
+                    pktgpu.l4_checksum(hs, hch, which, True, **hkw)
+                    ok = ok and np.array_equal(work[0].cpu().numpy().reshape(-1), hs.reshape(-1))
+                else:
+                    ok = all(np.array_equal(got[k], twin[k]) for k in got)
+                hist = {schema.L4_STATUS[k]: int((twin["status"] == k).sum()) for k in range(7) if (twin["status"] == k).any()}
+                line(f"l4_{'update' if upd else 'verify'}_{tag}", n, ms, read_b, 5 + (2 * float(summed.mean()) if upd else 0), cpu,
+                     {"parity_vs_host_twin": bool(ok), "which": which, "status_counts": hist,
+                      "measured": "min of 3 rounds of HIP events over back-to-back launches, one stream, a ring of "
+                                  f"{len(work)} copies of the batch, arguments marshalled once"})
+                del work, prep
+
+        l4_lines("c2", slabs, [dict(stride=64) for _ in slabs], c2, dict(stride=64), 0, chains, 0)
+        s4, o4, l4 = gen.gen_c4(n)
+        d4 = [torch.from_numpy(s4).to(dev) for _ in range(min(4, max(2, (1 << 30) // s4.size + 1)))]
+        do4, dl4 = torch.from_numpy(o4).to(dev), torch.from_numpy(l4).to(dev)
+        ch4 = [P.parse(d_, offsets=do4, lens=dl4, columns=["chain"]) for d_ in d4]
+        torch.cuda.synchronize()
+        l4_lines("c4", d4, [dict(offsets=do4, lens=dl4) for _ in d4], s4, dict(offsets=o4, lens=l4), schema.L4_LAST, ch4, 8 + 4)
+        del d4, ch4
     if want("edit"):
         import ctypes
         CH = ("status", "n_hdrs", "hdr_type", "hdr_off", "payload_off", "payload_len")
