@@ -257,6 +257,18 @@ class Parser {
               ctx_, "pkt_edit_batch");
     }
 
+    // Every packet's flow key (pkt_flow_key_batch): addresses, ports, protocol and IP version of the
+    // which_ip-th IPv4 / IPv6 header of `chain` (PKT_FLOW_LAST: the innermost), its 64-bit hash under `seed`
+    // and, with a 40-byte rss_key, the Toeplitz hash NICs compute.  flags: PKT_FLOW_SYMMETRIC | _NO_PORTS.
+    // Device arrays of n, each may be NULL; they are what pkt_flow_table_update takes.  Asynchronous on `s`.
+    void flow_keys(const pkt_batch_t& b, const pkt_chain_t& chain, pkt_flow_key_t* keys, uint64_t* hash,
+                   uint8_t* dir = nullptr, uint32_t* plen = nullptr, uint8_t* status = nullptr,
+                   uint32_t which_ip = PKT_FLOW_LAST, uint32_t flags = 0, uint64_t seed = 0, uint32_t* rss = nullptr,
+                   const uint8_t* rss_key = nullptr, hipStream_t s = nullptr) {
+        check(pkt_flow_key_batch(ctx_, &b, &chain, which_ip, flags, seed, rss_key, keys, hash, rss, dir, plen, status, s),
+              ctx_, "pkt_flow_key_batch");
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

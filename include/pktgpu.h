@@ -739,6 +739,118 @@ int pkt_l4_checksum_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_ch
 int pkt_l4_checksum_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which,
                          uint32_t flags, uint16_t *calc, uint16_t *stored, uint8_t *l4_status);
 
+/* ---- flow keys of a batch, and a flow table that accumulates them ----
+ * Which flow each packet belongs to, and how many packets and bytes each flow has carried.  The reference
+ * defines nothing here (it is a packet library, not a dataplane), so this header fixes the semantics; the one
+ * outside standard, the Toeplitz hash NICs compute for RSS, is matched bit for bit.  Two pieces that meet at
+ * caller-owned arrays: a stateless key kernel over a parsed batch, and a hash table over keys that never sees
+ * packets or chains.
+ *
+ * pkt_flow_key_batch
+ *  - batch / chain: any pkt_batch_t under its usual slab rules, with the chain columns of a parse of it, of a
+ *    stream's columns over pkt_pcap_stream_batch, or pkt_edit_batch's out_chain.  n_hdrs is taken as
+ *    min(n_hdrs, PKT_MAX_HDRS).  Whatever the columns hold, no byte outside the packet is used.
+ *  - The IP header is the `which_ip`-th list entry of type IPv4 or IPv6, the two counted together from 0;
+ *    PKT_FLOW_LAST takes the last such entry (a VXLAN packet's outer IP is 0, its inner IP is 1 and LAST).
+ *    `which_ip` in 16..0xFE is PKT_ERR_INVALID_ARG.  No such entry (n_hdrs == 0 included): PKT_FLOW_NO_IP.
+ *    The entry's 20 / 40 bytes not inside the packet (its length under the pkt_batch_t clamp): PKT_FLOW_SPAN.
+ *  - Ports are taken iff the list entry right after the IP entry is TCP or UDP, PKT_FLOW_NO_PORTS is not
+ *    set and, for IPv4, (bytes 6..7 & 0x3FFF) == 0 (pkt_l4_checksum_batch's fragment test: every fragment
+ *    of a datagram gets one key).  Ports that are taken are the 4 bytes at that entry's hdr_off; if they do
+ *    not lie inside the packet the status is PKT_FLOW_SPAN.  Not taken: sport = dport = 0.  proto is always
+ *    the IP header's own byte, so a GRE or ICMP packet keys on addresses and protocol alone.
+ *  - PKT_FLOW_SYMMETRIC: if the byte string src[16] | sport (big-endian) compares greater than dst[16] |
+ *    dport, the two ends are swapped and dir = 1; otherwise, and always without the flag, dir = 0.  Both
+ *    directions of a connection then give the same key, hash and rss.
+ *  - hash: h = seed; for each of the five little-endian u64 words w of the key as it lies in memory,
+ *    h = splitmix64(h ^ w) (splitmix64: the function spelled out at PKT_GEN_RANDOM).
+ *  - rss (computed iff rss != NULL): the Toeplitz hash of Microsoft RSS with the 40-byte `rss_key` (HOST
+ *    memory, captured at the call; may be NULL iff rss == NULL) over the key after any swap: src | dst (4 or
+ *    16 wire bytes each), then sport | dport (big-endian) iff ports were taken: 8, 12, 32 or 36 bytes.  For
+ *    each set input bit b, MSB first, the result is XORed with the 32 bits of rss_key that start at bit b.
+ *  - plen: the packet's length under the batch clamp rules (the table's byte weight for fixed-stride callers).
+ *  - A packet whose status is not PKT_FLOW_OK has an all-zero key and hash = rss = dir = 0; plen is written.
+ *  - keys / hash / rss / dir / plen / status: device [n], each may be NULL.
+ *  - PKT_ERR_INVALID_ARG, before any launch: pkt_l4_checksum_batch's refusals (batch and slab rules, a NULL
+ *    chain or, with n > 0, chain column, n >= 2^32, unknown flag bits, a bad which_ip), rss without rss_key,
+ *    keys not 2-byte aligned.  n == 0 succeeds and launches nothing.
+ * Asynchronous on `stream`; keeps no ctx state.  pkt_flow_key_host: the same on HOST pointers, no device. */
+typedef struct pkt_flow_key {      /* 40 bytes */
+    uint8_t  src[16];              /* wire bytes; IPv4 in [0..4), the rest 0 */
+    uint8_t  dst[16];
+    uint16_t sport;                /* values (host order); 0 when not taken */
+    uint16_t dport;
+    uint8_t  proto;                /* IPv4 byte 9 / IPv6 byte 6, as read */
+    uint8_t  ipver;                /* 4 or 6 */
+    uint16_t zero;
+} pkt_flow_key_t;
+typedef enum pkt_flow_status {
+    PKT_FLOW_OK    = 0,
+    PKT_FLOW_NO_IP = 1, /* the chain has no such IPv4 / IPv6 entry */
+    PKT_FLOW_SPAN  = 2  /* the IP header, or the ports that would be taken, do not lie inside the packet */
+} pkt_flow_status_t;
+#define PKT_FLOW_LAST       0xFFu  /* which_ip: the last (innermost) IPv4 / IPv6 entry of the list */
+#define PKT_FLOW_SYMMETRIC  1u     /* flags: order the two ends, so both directions share a key */
+#define PKT_FLOW_NO_PORTS   2u     /* flags: never take ports */
+size_t pkt_sizeof_flow_key(void);
+int pkt_flow_key_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                       uint32_t flags, uint64_t seed, const uint8_t rss_key[40], pkt_flow_key_t *keys,
+                       uint64_t *hash, uint32_t *rss, uint8_t *dir, uint32_t *plen, uint8_t *status, void *stream);
+int pkt_flow_key_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip, uint32_t flags,
+                      uint64_t seed, const uint8_t rss_key[40], pkt_flow_key_t *keys, uint64_t *hash,
+                      uint32_t *rss, uint8_t *dir, uint32_t *plen, uint8_t *status);
+
+/* pkt_flow_table_*: an open-addressing table of `slots` entries (a power of two, 64..2^28; 128 bytes each) that
+ * the handle owns, in the memory of the ctx's device (create) or in host memory (create_host: every call
+ * then takes HOST pointers, runs a sequential loop and touches no device).  No memory is allocated in any
+ * call after create.  One call at a time per table.
+ *  - update (asynchronous; [n] arrays, n < 2^32): keys (8-byte aligned) and hash are required; dir NULL =
+ *    every packet is direction 0 (otherwise its bit 0 counts); weight NULL = bytes are not counted; status
+ *    NULL = every packet is OK; flow_id and upd_status may each be NULL.  Packet i has the global index
+ *    base + i, and base must be >= the previous update's base + n on this table (the table keeps that
+ *    high-water mark, clear resets it), else PKT_ERR_INVALID_ARG.
+ *  - tag = hash & mask(tag_bits), 0 mapped to 1.  Probing starts at splitmix64(tag) & (slots - 1) and is
+ *    linear.  An entry belongs to one tag; its key is the key of the first packet, by base + i, that ever
+ *    reached it.  A packet whose key equals its entry's key is PKT_FLOW_UPD_OK: pkts[dir] += 1, bytes[dir] +=
+ *    weight, flow_id = the slot.  One with the same tag and another key is PKT_FLOW_UPD_COLLISION and is
+ *    counted nowhere (at 64 tag bits that needs a 64-bit hash collision; set_tag_bits, 1..64, allowed on a
+ *    table that has seen no update since create / clear, lets a test make them happen).  A tag that finds
+ *    neither its entry nor an empty slot in `slots` probes makes its packets PKT_FLOW_UPD_FULL: which tags
+ *    lose when the table fills is unspecified, the entries the table holds stay exact.  A packet with
+ *    status[i] != 0 is PKT_FLOW_UPD_SKIPPED.  flow_id is 0xFFFFFFFF for every packet that is not UPD_OK.
+ *  - Counters are integer atomics: exact.  Slot numbers may differ from run to run, the set of records not.
+ *  - count (blocking): the number of entries.  export (blocking): the entries in ascending slot order,
+ *    min(cap, count) records written, *n_out = count.  clear (asynchronous): the empty table.
+ *  - On the device, update is three launches (claim the entry and its lowest index; the packet with that
+ *    index stores the key; compare and count), the kernel boundaries publish the data: no lane ever waits
+ *    for another; a wave adds once per entry and direction it holds, a block of packets of one flow once. */
+typedef struct pkt_flow_table pkt_flow_table_t;
+typedef struct pkt_flow_record {   /* 80 bytes */
+    pkt_flow_key_t key;
+    uint64_t first;                /* lowest base + i of the flow's packets */
+    uint64_t pkts[2];              /* by dir */
+    uint64_t bytes[2];
+} pkt_flow_record_t;
+typedef enum pkt_flow_upd {
+    PKT_FLOW_UPD_OK        = 0,
+    PKT_FLOW_UPD_SKIPPED   = 1,
+    PKT_FLOW_UPD_COLLISION = 2,
+    PKT_FLOW_UPD_FULL      = 3
+} pkt_flow_upd_t;
+size_t pkt_sizeof_flow_record(void);
+int pkt_flow_table_create(pkt_ctx_t *ctx, uint64_t slots, pkt_flow_table_t **table);
+int pkt_flow_table_create_host(uint64_t slots, pkt_flow_table_t **table);
+int pkt_flow_table_set_tag_bits(pkt_flow_table_t *table, uint32_t bits);
+int pkt_flow_table_update(pkt_flow_table_t *table, const pkt_flow_key_t *keys, const uint64_t *hash,
+                          const uint8_t *dir, const uint32_t *weight, const uint8_t *status, uint64_t n,
+                          uint64_t base, uint32_t *flow_id, uint8_t *upd_status, void *stream);
+int pkt_flow_table_count(pkt_flow_table_t *table, uint64_t *flows, void *stream);
+int pkt_flow_table_export(pkt_flow_table_t *table, pkt_flow_record_t *records, uint64_t cap, uint64_t *n_out,
+                          void *stream);
+int pkt_flow_table_clear(pkt_flow_table_t *table, void *stream);
+int pkt_flow_table_destroy(pkt_flow_table_t *table);
+const char *pkt_flow_table_last_error(const pkt_flow_table_t *table);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -1,9 +1,11 @@
 // pktgpu_host.cpp — host-side part of the C ABI: metadata tables, the pcap indexer and the
 // host checksum.  No device code.
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/pktgpu.h"
 #include "pktgpu_batch.hpp"
+#include "pktgpu_flow.hpp"
 
 namespace {
 
@@ -431,6 +433,246 @@ int pkt_l4_checksum_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_
     }
     return PKT_SUCCESS;
 }
+
+// pkt_flow_key_batch on host pointers (the CPU model of pktgpu_flow.hip's key kernel), byte by byte.
+int pkt_flow_key_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags, uint64_t seed,
+                      const uint8_t rss_key[40], pkt_flow_key_t* keys, uint64_t* hash, uint32_t* rss, uint8_t* dir,
+                      uint32_t* plen, uint8_t* status) {
+    if (!b || !chain) return PKT_ERR_INVALID_ARG;
+    if (b->n >= (1ull << 32) || (flags & ~(PKT_FLOW_SYMMETRIC | PKT_FLOW_NO_PORTS))) return PKT_ERR_INVALID_ARG;
+    if (which_ip >= PKT_MAX_HDRS && which_ip != PKT_FLOW_LAST) return PKT_ERR_INVALID_ARG;
+    if ((rss && !rss_key) || ((uintptr_t)keys & 1)) return PKT_ERR_INVALID_ARG;
+    const uint64_t n = b->n;
+    if (n == 0) return PKT_SUCCESS;
+    if (bad_batch(b) || !chain->n_hdrs || !chain->hdr_type || !chain->hdr_off) return PKT_ERR_INVALID_ARG;
+    const BatchSrc src = batch_src(b);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t off = pkt_off(src, i);
+        const uint32_t len = pkt_len(src, i, off);
+        uint32_t nh = chain->n_hdrs[i], seen = 0, slot = PKT_MAX_HDRS;
+        nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+        for (uint32_t j = 0; j < nh; j++) {
+            const uint8_t t = chain->hdr_type[j * n + i];
+            if (t != PKT_HDR_IPV4 && t != PKT_HDR_IPV6) continue;
+            if (which_ip == PKT_FLOW_LAST || seen == which_ip) slot = j;
+            seen++;
+        }
+        uint8_t k[40] = {};  // the key as it lies in memory
+        uint32_t st = PKT_FLOW_NO_IP, d = 0, r = 0;
+        uint64_t h = 0;
+        if (slot < PKT_MAX_HDRS) {
+            const bool v4 = chain->hdr_type[slot * n + i] == PKT_HDR_IPV4;
+            const uint32_t ip = chain->hdr_off[slot * n + i], alen = v4 ? 4u : 16u;
+            const uint8_t* p = b->slab + off;
+            st = PKT_FLOW_OK;
+            bool ports = false;
+            uint32_t l4 = 0;
+            if (ip + (v4 ? 20u : 40u) > len) {
+                st = PKT_FLOW_SPAN;
+            } else {
+                const uint8_t nt = slot + 1 < nh ? chain->hdr_type[(slot + 1) * n + i] : 0;
+                l4 = slot + 1 < nh ? chain->hdr_off[(slot + 1) * n + i] : 0u;
+                ports = (nt == PKT_HDR_TCP || nt == PKT_HDR_UDP) && !(flags & PKT_FLOW_NO_PORTS) &&
+                        !(v4 && ((((uint32_t)p[ip + 6] << 8) | p[ip + 7]) & 0x3FFFu));
+                if (ports && l4 + 4u > len) st = PKT_FLOW_SPAN;
+            }
+            if (st == PKT_FLOW_OK) {
+                const uint8_t* a = p + ip + (v4 ? 12 : 8);
+                uint8_t e0[18] = {}, e1[18] = {};  // src | sport, dst | dport: big-endian byte strings
+                memcpy(e0, a, alen);
+                memcpy(e1, a + alen, alen);
+                if (ports) {
+                    memcpy(e0 + 16, p + l4, 2);
+                    memcpy(e1 + 16, p + l4 + 2, 2);
+                }
+                if ((flags & PKT_FLOW_SYMMETRIC) && memcmp(e0, e1, 18) > 0) {
+                    uint8_t t[18];
+                    memcpy(t, e0, 18);
+                    memcpy(e0, e1, 18);
+                    memcpy(e1, t, 18);
+                    d = 1;
+                }
+                memcpy(k, e0, 16);
+                memcpy(k + 16, e1, 16);
+                k[32] = e0[17];  // sport and dport as little-endian values
+                k[33] = e0[16];
+                k[34] = e1[17];
+                k[35] = e1[16];
+                k[36] = p[ip + (v4 ? 9 : 6)];
+                k[37] = v4 ? 4 : 6;
+                uint64_t w[5];
+                for (int q = 0; q < 5; q++) {
+                    w[q] = 0;
+                    for (int z = 7; z >= 0; z--) w[q] = w[q] << 8 | k[8 * q + z];
+                }
+                h = flow_hash(seed, w);
+                if (rss) {
+                    uint8_t in[36];
+                    uint32_t m = 0;
+                    memcpy(in, e0, alen);
+                    memcpy(in + alen, e1, alen);
+                    m = 2 * alen;
+                    if (ports) {
+                        memcpy(in + m, e0 + 16, 2);
+                        memcpy(in + m + 2, e1 + 16, 2);
+                        m += 4;
+                    }
+                    // bit by bit: the 32 key bits that start at input bit 8 * x + y
+                    for (uint32_t x = 0; x < m; x++)
+                        for (uint32_t y = 0; y < 8; y++) {
+                            if (!(in[x] & (0x80u >> y))) continue;
+                            uint32_t win = 0;
+                            for (uint32_t z = 0; z < 32; z++) {
+                                const uint32_t bit = 8 * x + y + z;
+                                const uint32_t kb = bit < 320 ? (rss_key[bit >> 3] >> (7 - (bit & 7))) & 1u : 0u;
+                                win = win << 1 | kb;
+                            }
+                            r ^= win;
+                        }
+                }
+            }
+        }
+        if (keys) memcpy(reinterpret_cast<uint8_t*>(keys) + 40 * i, k, 40);
+        if (hash) hash[i] = h;
+        if (rss) rss[i] = r;
+        if (dir) dir[i] = (uint8_t)d;
+        if (plen) plen[i] = len;
+        if (status) status[i] = (uint8_t)st;
+    }
+    return PKT_SUCCESS;
+}
+
+// ---- the flow table: the public calls, and the host table as a sequential loop (the device table: pktgpu_flow.hip)
+size_t pkt_sizeof_flow_key(void) { return sizeof(pkt_flow_key_t); }
+size_t pkt_sizeof_flow_record(void) { return sizeof(pkt_flow_record_t); }
+
+int pkt_flow_table_create_host(uint64_t slots, pkt_flow_table_t** out) {
+    if (!out) return PKT_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (slots < kFlowMinSlots || slots > kFlowMaxSlots || (slots & (slots - 1))) return PKT_ERR_INVALID_ARG;
+    pkt_flow_table* t = new pkt_flow_table;
+    t->slots = slots;
+    t->e = static_cast<FlowEntry*>(aligned_alloc(alignof(FlowEntry), slots * sizeof(FlowEntry)));
+    if (!t->e) {
+        delete t;
+        return PKT_ERR_UNSUPPORTED;
+    }
+    *out = t;
+    return pkt_flow_table_clear(t, nullptr);
+}
+
+int pkt_flow_table_set_tag_bits(pkt_flow_table_t* t, uint32_t bits) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (bits < 1 || bits > 64) return flow_fail(t, PKT_ERR_INVALID_ARG, "pkt_flow_table_set_tag_bits: bits not in 1..64");
+    if (t->touched) return flow_fail(t, PKT_ERR_INVALID_ARG, "pkt_flow_table_set_tag_bits: the table is not empty");
+    t->tag_bits = bits;
+    return PKT_SUCCESS;
+}
+
+int pkt_flow_table_update(pkt_flow_table_t* t, const pkt_flow_key_t* keys, const uint64_t* hash, const uint8_t* dir,
+                          const uint32_t* weight, const uint8_t* status, uint64_t n, uint64_t base, uint32_t* flow_id,
+                          uint8_t* upd_status, void* stream) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (n >= (1ull << 32)) return flow_fail(t, PKT_ERR_INVALID_ARG, "pkt_flow_table_update: n >= 2^32");
+    if (base < t->hwm || base + n < base)
+        return flow_fail(t, PKT_ERR_INVALID_ARG, "pkt_flow_table_update: base below the previous update's base + n");
+    if (n && (!keys || !hash)) return flow_fail(t, PKT_ERR_INVALID_ARG, "pkt_flow_table_update: null keys or hash");
+    if ((uintptr_t)keys & 7) return flow_fail(t, PKT_ERR_INVALID_ARG, "pkt_flow_table_update: keys not 8-byte aligned");
+    const FlowUpdate u{keys, hash, dir, weight, status, n, base, flow_id, upd_status};
+    if (n && t->ops) {
+        const int rc = t->ops->update(t, u, stream);
+        if (rc != PKT_SUCCESS) return rc;
+    }
+    for (uint64_t i = 0; !t->ops && i < n; i++) {  // the host table
+        uint32_t id = kFlowNone, st = PKT_FLOW_UPD_FULL;
+        if (status && status[i]) {
+            st = PKT_FLOW_UPD_SKIPPED;
+        } else {
+            uint64_t w[5];
+            memcpy(w, reinterpret_cast<const uint8_t*>(keys) + 40 * i, 40);
+            const uint64_t tag = flow_tag(hash[i], t->tag_bits);
+            uint64_t pos = flow_home(tag, t->slots);
+            for (uint64_t probes = 0; probes < t->slots; probes++, pos = (pos + 1) & (t->slots - 1)) {
+                FlowEntry& e = t->e[pos];
+                if (e.tag == 0) {  // in index order: the first packet to reach an entry is its lowest index
+                    e.tag = tag;
+                    e.first = base + i;
+                    memcpy(e.key, w, 40);
+                }
+                if (e.tag != tag) continue;
+                if (memcmp(e.key, w, 40) != 0) {
+                    st = PKT_FLOW_UPD_COLLISION;
+                } else {
+                    const uint32_t d = dir ? dir[i] & 1u : 0u;
+                    e.pkts[d] += 1;
+                    e.bytes[d] += weight ? weight[i] : 0u;
+                    id = (uint32_t)pos;
+                    st = PKT_FLOW_UPD_OK;
+                }
+                break;
+            }
+        }
+        if (flow_id) flow_id[i] = id;
+        if (upd_status) upd_status[i] = (uint8_t)st;
+    }
+    t->hwm = base + n;
+    if (n) t->touched = true;
+    return PKT_SUCCESS;
+}
+
+int pkt_flow_table_export(pkt_flow_table_t* t, pkt_flow_record_t* records, uint64_t cap, uint64_t* n_out, void* stream) {
+    if (!t || !n_out) return PKT_ERR_INVALID_ARG;
+    if (cap && !records) return flow_fail(t, PKT_ERR_INVALID_ARG, "pkt_flow_table_export: null records");
+    if (t->ops) return t->ops->scan(t, records, cap, n_out, stream);
+    uint64_t k = 0;
+    for (uint64_t s = 0; s < t->slots; s++) {
+        const FlowEntry& e = t->e[s];
+        if (!e.tag) continue;
+        if (k < cap) {
+            pkt_flow_record_t& r = records[k];
+            memcpy(&r.key, e.key, 40);
+            r.first = e.first;
+            for (int d = 0; d < 2; d++) {
+                r.pkts[d] = e.pkts[d];
+                r.bytes[d] = e.bytes[d];
+            }
+        }
+        k++;
+    }
+    *n_out = k;
+    return PKT_SUCCESS;
+}
+
+int pkt_flow_table_count(pkt_flow_table_t* t, uint64_t* flows, void* stream) {
+    return pkt_flow_table_export(t, nullptr, 0, flows, stream);
+}
+
+int pkt_flow_table_clear(pkt_flow_table_t* t, void* stream) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (t->ops) {
+        const int rc = t->ops->clear(t, stream);
+        if (rc != PKT_SUCCESS) return rc;
+    } else {
+        memset(static_cast<void*>(t->e), 0, t->slots * sizeof(FlowEntry));
+        for (uint64_t s = 0; s < t->slots; s++) t->e[s].first = ~0ull;
+    }
+    t->hwm = 0;
+    t->touched = false;
+    return PKT_SUCCESS;
+}
+
+int pkt_flow_table_destroy(pkt_flow_table_t* t) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    int rc = PKT_SUCCESS;
+    if (t->ops)
+        rc = t->ops->destroy(t);
+    else
+        free(t->e);
+    delete t;
+    return rc;
+}
+
+const char* pkt_flow_table_last_error(const pkt_flow_table_t* t) { return t ? t->err.c_str() : "null table"; }
 
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,
 // packet.rs:724-731: insert / set_payload).

@@ -25,7 +25,7 @@ from . import schema
 from .schema import (ABI_VERSION, DEPTH_LIMIT, ENTRIES, ENTRY_ID, GROUPS, HDR_ID, HDR_NAMES,  # noqa: F401
                      HDR_SIZES, MAX_HDRS, OK, STATUS_NAMES, TRUNCATED)
 
-__all__ = ["Parser", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
+__all__ = ["Parser", "FlowTable", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
 
 
 def resolve_columns(columns):
@@ -660,6 +660,42 @@ class Parser:
         self._check(self._L.pkt_l4_checksum_batch(self._ctx, *args, self._stream(stream)), "pkt_l4_checksum_batch")
         return {"calc": out[0], "stored": out[1], "status": out[2]}
 
+    def _flow_args(self, slab, chain, which_ip=schema.FLOW_LAST, symmetric=False, ports=True, seed=0, rss_key=None,
+                   stride=None, n=None, offsets=None, lens=None, outputs=(True,) * 6):
+        """The marshalled arguments of pkt_flow_key_batch (after ctx, before stream); `outputs`: whether keys,
+        hash, rss, dir, plen and status are asked for (rss only with an rss_key)."""
+        torch = _torch()
+        b = self._batch(slab, n, stride, offsets, lens)
+        ch = self._chain(chain)
+        flags = (schema.FLOW_SYMMETRIC if symmetric else 0) | (0 if ports else schema.FLOW_NO_PORTS)
+        rk = _rss_key(rss_key)
+        shapes = (((b.n, 40), torch.uint8), ((b.n,), torch.uint64), ((b.n,), torch.uint32), ((b.n,), torch.uint8),
+                  ((b.n,), torch.uint32), ((b.n,), torch.uint8))
+        want = list(outputs)
+        want[2] = want[2] and rk is not None
+        out = tuple(torch.empty(shp, dtype=dt, device=self.torch_device) if w else None
+                    for (shp, dt), w in zip(shapes, want))
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), flags, int(seed), rk, *[ptr(t) for t in out])
+        return args, out, (b, ch, rk)
+
+    def flow_keys(self, slab, chain, which_ip=schema.FLOW_LAST, symmetric=False, ports=True, seed=0, rss_key=None,
+                  stride=None, n=None, offsets=None, lens=None, stream=None):
+        """pkt_flow_key_batch: every packet's flow key -> {"keys": uint8 [n, 40] (pkt_flow_key_t:
+        schema.FLOW_KEY_DTYPE), "hash": uint64, "rss": uint32 (only with an `rss_key` of 40 bytes: the
+        Toeplitz hash NICs compute), "dir": uint8, "plen": uint32, "status": uint8 (pktgpu.FLOW_OK / _NO_IP /
+        _SPAN)}.  `chain`: the chain columns of a parse of the batch, a stream's columns over its batch(), or
+        edit's out chain.  `which_ip`: the k-th IPv4 / IPv6 header of the list, counted together from 0, or
+        pktgpu.FLOW_LAST (the innermost).  symmetric=True orders the two ends, so both directions of a
+        connection share a key and `dir` tells them apart; ports=False keys on addresses and protocol alone.
+        The dict is what FlowTable.update takes.  Asynchronous on `stream`."""
+        args, out, keep = self._flow_args(slab, chain, which_ip, symmetric, ports, seed, rss_key, stride, n, offsets, lens)
+        self._check(self._L.pkt_flow_key_batch(self._ctx, *args, self._stream(stream)), "pkt_flow_key_batch")
+        res = dict(zip(("keys", "hash", "rss", "dir", "plen", "status"), out))
+        if res["rss"] is None:
+            del res["rss"]
+        return res
+
     def pcap_index_device_timed(self, buf, offsets, lens, stream=None):
         """pkt_pcap_index_device_timed into the caller's device `offsets` / `lens` (cap = their
         length): (record count, [guess, scan, emit] kernel ms from HIP events between them)."""
@@ -916,6 +952,171 @@ def l4_checksum(slab, chain, which=0, update=False, keep_zero_udp=False, stride=
     if rc != 0:
         raise ValueError(f"pkt_l4_checksum_host failed ({rc})")
     return {"calc": calc, "stored": stored, "status": status}
+
+
+FLOW_OK, FLOW_NO_IP, FLOW_SPAN = range(3)
+FLOW_LAST = schema.FLOW_LAST
+FLOW_UPD_OK, FLOW_UPD_SKIPPED, FLOW_UPD_COLLISION, FLOW_UPD_FULL = range(4)
+FLOW_NONE = schema.FLOW_NONE
+
+
+def _rss_key(rss_key):
+    """A 40-byte Toeplitz key as a ctypes buffer (None stays None)."""
+    if rss_key is None:
+        return None
+    raw = bytes(rss_key)
+    if len(raw) != 40:
+        raise ValueError(f"rss_key: 40 bytes, got {len(raw)}")
+    return ctypes.create_string_buffer(raw, 40)
+
+
+def flow_keys(slab, chain, which_ip=FLOW_LAST, symmetric=False, ports=True, seed=0, rss_key=None, stride=None, n=None,
+              offsets=None, lens=None):
+    """pkt_flow_key_host over numpy arrays (no device): Parser.flow_keys's arguments with numpy arrays ->
+    the same dict of numpy arrays, which a host FlowTable (FlowTable(None, slots)) takes."""
+    from . import _lib
+    L = _lib.load()
+    b, keep = _host_batch(_lib, dict(slab=slab, stride=stride, n=n, offsets=offsets, lens=lens))
+    cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+            np.ascontiguousarray(chain["hdr_off"], np.uint16))
+    ch = _lib.PktChain(*[c.ctypes.data for c in cols])
+    flags = (schema.FLOW_SYMMETRIC if symmetric else 0) | (0 if ports else schema.FLOW_NO_PORTS)
+    rk = _rss_key(rss_key)
+    res = {"keys": np.zeros((b.n, 40), np.uint8), "hash": np.zeros(b.n, np.uint64), "rss": np.zeros(b.n, np.uint32),
+           "dir": np.zeros(b.n, np.uint8), "plen": np.zeros(b.n, np.uint32), "status": np.zeros(b.n, np.uint8)}
+    if rk is None:
+        del res["rss"]
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    rc = L.pkt_flow_key_host(ctypes.byref(b), ctypes.byref(ch), int(which_ip), flags, int(seed), rk, ptr(res["keys"]),
+                             ptr(res["hash"]), ptr(res.get("rss")), ptr(res["dir"]), ptr(res["plen"]), ptr(res["status"]))
+    if rc != 0:
+        raise ValueError(f"pkt_flow_key_host failed ({rc})")
+    return res
+
+
+class FlowTable:
+    """pkt_flow_table_*: per-flow packet and byte counters that persist from one batch (or stream window) to
+    the next.  FlowTable(parser, slots) lives on the parser's device and takes Parser.flow_keys's dict of
+    device tensors; FlowTable(None, slots) is the host table over pktgpu.flow_keys's numpy arrays.  `slots`: a
+    power of two in 64..2^28, 128 bytes each; the table only grows until clear().
+
+        keys = p.flow_keys(slab, chain, symmetric=True, offsets=offs, lens=lens)
+        flow_id, upd = table.update(keys, base=records_so_far)
+        table.flows()   # {"key", "first", "pkts", "bytes"} sorted by first
+    """
+
+    def __init__(self, parser, slots):
+        from . import _lib
+        self._lib = _lib
+        self._L = _lib.load()
+        self.parser = parser
+        h = ctypes.c_void_p()
+        if parser is None:
+            rc = self._L.pkt_flow_table_create_host(int(slots), ctypes.byref(h))
+            if rc != 0:
+                raise ValueError(f"pkt_flow_table_create_host({slots}) failed ({rc})")
+        else:
+            parser._check(self._L.pkt_flow_table_create(parser._ctx, int(slots), ctypes.byref(h)), "pkt_flow_table_create")
+        self._t = h
+        self.slots = int(slots)
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self._L.pkt_flow_table_last_error(self._t)
+            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+    def _stream(self, stream):
+        return None if self.parser is None else self.parser._stream(stream)
+
+    def set_tag_bits(self, bits):
+        """pkt_flow_table_set_tag_bits: the low `bits` (1..64) of the hash are the tag; on an empty table."""
+        self._check(self._L.pkt_flow_table_set_tag_bits(self._t, int(bits)), "pkt_flow_table_set_tag_bits")
+
+    def _update_args(self, keys, weight="plen", base=0, outputs=(True, True)):
+        """The marshalled arguments of pkt_flow_table_update (after the table, before stream)."""
+        host = self.parser is None
+        k = keys["keys"]
+        n = int(k.shape[0])
+        if isinstance(weight, str):
+            weight = keys[weight]
+        cols = [k, keys["hash"], keys.get("dir"), weight, keys.get("status")]
+        if host:
+            dts = (np.uint8, np.uint64, np.uint8, np.uint32, np.uint8)
+            cols = [None if c is None else np.ascontiguousarray(c, dt) for c, dt in zip(cols, dts)]
+            out = (np.zeros(n, np.uint32) if outputs[0] else None, np.zeros(n, np.uint8) if outputs[1] else None)
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        else:
+            torch = _torch()
+            dts = (torch.uint8, torch.uint64, torch.uint8, torch.uint32, torch.uint8)
+            for c, dt in zip(cols, dts):
+                assert c is None or (c.is_cuda and c.dtype == dt and c.is_contiguous())
+            dev = self.parser.torch_device
+            out = (torch.empty(n, dtype=torch.uint32, device=dev) if outputs[0] else None,
+                   torch.empty(n, dtype=torch.uint8, device=dev) if outputs[1] else None)
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        for c in cols[1:]:
+            assert c is None or c.shape[0] == n
+        args = (*[ptr(c) for c in cols], n, int(base), ptr(out[0]), ptr(out[1]))
+        return args, out, cols
+
+    def update(self, keys, weight="plen", base=0, stream=None):
+        """pkt_flow_table_update with flow_keys's dict -> (flow_id uint32, upd_status uint8): FLOW_UPD_OK
+        (counted; flow_id = its slot), _SKIPPED (status != 0), _COLLISION (its tag's entry holds another
+        key), _FULL; flow_id is pktgpu.FLOW_NONE unless OK.  `weight`: the name of the dict's byte column
+        ("plen"), an array of uint32, or None (bytes are not counted).  `base`: the global index of packet 0,
+        at least the previous update's base + n (a stream: its released_records).  Asynchronous on `stream`."""
+        args, out, keep = self._update_args(keys, weight, base)
+        self._check(self._L.pkt_flow_table_update(self._t, *args, self._stream(stream)), "pkt_flow_table_update")
+        return out
+
+    def count(self, stream=None):
+        """pkt_flow_table_count: the number of flows (waits for `stream`)."""
+        k = ctypes.c_uint64()
+        self._check(self._L.pkt_flow_table_count(self._t, ctypes.byref(k), self._stream(stream)), "pkt_flow_table_count")
+        return k.value
+
+    def export(self, cap=None, stream=None):
+        """pkt_flow_table_export: (records in slot order as a schema.FLOW_RECORD_DTYPE array of min(cap,
+        count) rows, count).  cap=None: every record."""
+        if cap is None:
+            cap = self.count(stream)
+        cap = int(cap)
+        k = ctypes.c_uint64()
+        if self.parser is None:
+            buf = np.zeros(cap * 80, np.uint8)
+            p = buf.ctypes.data if cap else None
+        else:
+            torch = _torch()
+            buf = torch.zeros(cap * 80, dtype=torch.uint8, device=self.parser.torch_device)
+            p = buf.data_ptr() if cap else None
+        self._check(self._L.pkt_flow_table_export(self._t, p, cap, ctypes.byref(k), self._stream(stream)),
+                    "pkt_flow_table_export")
+        if self.parser is not None:
+            buf = buf.cpu().numpy()
+        return buf.view(schema.FLOW_RECORD_DTYPE)[:min(cap, k.value)], k.value
+
+    def flows(self, stream=None):
+        """The records sorted by `first` (unique per flow: the order is the same from run to run) ->
+        {"key": uint8 [k, 40], "first": uint64, "pkts": uint64 [k, 2], "bytes": uint64 [k, 2]}, numpy."""
+        rec, _ = self.export(None, stream)
+        rec = rec[np.argsort(rec["first"], kind="stable")]
+        key = np.ascontiguousarray(rec["key"]).view(np.uint8).reshape(-1, 40)
+        return {"key": key, "first": rec["first"].copy(), "pkts": rec["pkts"].copy(), "bytes": rec["bytes"].copy()}
+
+    def clear(self, stream=None):
+        """pkt_flow_table_clear: the empty table; `base` may start again from 0."""
+        self._check(self._L.pkt_flow_table_clear(self._t, self._stream(stream)), "pkt_flow_table_clear")
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self._L.pkt_flow_table_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ----------------------------------------------------------------- PacketSlice-style host views

@@ -57,6 +57,17 @@ class PktGenField(ctypes.Structure):
                 ("base", ctypes.c_uint64), ("step", ctypes.c_uint64), ("count", ctypes.c_uint64)]
 
 
+class PktFlowKey(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_uint8 * 16), ("dst", ctypes.c_uint8 * 16), ("sport", ctypes.c_uint16),
+                ("dport", ctypes.c_uint16), ("proto", ctypes.c_uint8), ("ipver", ctypes.c_uint8),
+                ("zero", ctypes.c_uint16)]
+
+
+class PktFlowRecord(ctypes.Structure):
+    _fields_ = [("key", PktFlowKey), ("first", ctypes.c_uint64), ("pkts", ctypes.c_uint64 * 2),
+                ("bytes", ctypes.c_uint64 * 2)]
+
+
 # Every function declared in include/pktgpu.h: name -> (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -159,6 +170,21 @@ SIGNATURES = {
                                              ctypes.c_uint32, _P, _P, _P, _P]),
     "pkt_l4_checksum_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
                                             ctypes.c_uint32, _P, _P, _P]),
+    "pkt_sizeof_flow_key": (ctypes.c_size_t, []),
+    "pkt_flow_key_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                          ctypes.c_uint32, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pkt_flow_key_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P]),
+    "pkt_sizeof_flow_record": (ctypes.c_size_t, []),
+    "pkt_flow_table_create": (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.POINTER(_P)]),
+    "pkt_flow_table_create_host": (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(_P)]),
+    "pkt_flow_table_set_tag_bits": (ctypes.c_int, [_P, ctypes.c_uint32]),
+    "pkt_flow_table_update": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P]),
+    "pkt_flow_table_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), _P]),
+    "pkt_flow_table_export": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), _P]),
+    "pkt_flow_table_clear": (ctypes.c_int, [_P, _P]),
+    "pkt_flow_table_destroy": (ctypes.c_int, [_P]),
+    "pkt_flow_table_last_error": (ctypes.c_char_p, [_P]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -236,7 +262,9 @@ def load():
             or L.pkt_sizeof_gen_field() != ctypes.sizeof(PktGenField) \
             or L.pkt_sizeof_gather_piece() != ctypes.sizeof(PktGatherPiece) \
             or L.pkt_sizeof_cmp_summary() != ctypes.sizeof(PktCmpSummary) \
-            or L.pkt_sizeof_edit_op() != ctypes.sizeof(PktEditOp):
+            or L.pkt_sizeof_edit_op() != ctypes.sizeof(PktEditOp) \
+            or L.pkt_sizeof_flow_key() != ctypes.sizeof(PktFlowKey) \
+            or L.pkt_sizeof_flow_record() != ctypes.sizeof(PktFlowRecord):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L
     return L

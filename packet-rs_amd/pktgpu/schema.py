@@ -20,6 +20,20 @@ L4_STATUS = ["OK", "BAD", "UNCHECKED", "ABSENT", "NO_IP", "SPAN", "FRAGMENT"]
 L4_LAST = 0xFF
 L4_UPDATE, L4_KEEP_ZERO_UDP = 1, 2
 
+# pkt_flow_status_t, the flags and which_ip of pkt_flow_key_batch; pkt_flow_upd_t (pkt_flow_table_update)
+FLOW_OK, FLOW_NO_IP, FLOW_SPAN = range(3)
+FLOW_STATUS = ["OK", "NO_IP", "SPAN"]
+FLOW_LAST = 0xFF
+FLOW_SYMMETRIC, FLOW_NO_PORTS = 1, 2
+FLOW_UPD_OK, FLOW_UPD_SKIPPED, FLOW_UPD_COLLISION, FLOW_UPD_FULL = range(4)
+FLOW_UPD_STATUS = ["OK", "SKIPPED", "COLLISION", "FULL"]
+FLOW_NONE = 0xFFFFFFFF  # flow_id of a packet that is not FLOW_UPD_OK
+# pkt_flow_key_t / pkt_flow_record_t as numpy records
+FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
+                           ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])
+FLOW_RECORD_DTYPE = np.dtype([("key", FLOW_KEY_DTYPE), ("first", np.uint64), ("pkts", np.uint64, 2),
+                              ("bytes", np.uint64, 2)])
+
 # pkt_hdr_type_t -> Header::name() of the reference (headers.rs:529-827)
 HDR_NAMES = [
     "", "Ether", "Vlan", "IPv4", "IPv6", "ICMP", "TCP", "UDP", "ARP", "Vxlan", "Dot3",

@@ -18,10 +18,11 @@ C_SCALARS = {"uint8_t": "u8", "uint16_t": "u16", "uint32_t": "u32", "uint64_t": 
              "pkt_ctx_t": "PktCtx", "pkt_batch_t": "PktBatch", "pkt_out_t": "PktOut", "pkt_chain_t": "PktChain",
              "pkt_field_spec_t": "PktFieldSpec", "pkt_gen_field_t": "PktGenField", "pkt_gen_t": "PktGen",
              "pkt_mgpu_t": "PktMgpu", "pkt_gather_piece_t": "PktGatherPiece", "pkt_pcap_stream_t": "PktPcapStream",
-             "pkt_cmp_summary_t": "PktCmpSummary", "pkt_edit_op_t": "PktEditOp"}
+             "pkt_cmp_summary_t": "PktCmpSummary", "pkt_edit_op_t": "PktEditOp", "pkt_flow_key_t": "PktFlowKey",
+             "pkt_flow_record_t": "PktFlowRecord", "pkt_flow_table_t": "PktFlowTable"}
 STRUCTS = {"pkt_batch": "PktBatch", "pkt_out": "PktOut", "pkt_field_spec": "PktFieldSpec", "pkt_chain": "PktChain",
            "pkt_gen_field": "PktGenField", "pkt_gather_piece": "PktGatherPiece", "pkt_cmp_summary": "PktCmpSummary",
-           "pkt_edit_op": "PktEditOp"}
+           "pkt_edit_op": "PktEditOp", "pkt_flow_key": "PktFlowKey", "pkt_flow_record": "PktFlowRecord"}
 
 
 def _strip(src):
@@ -72,8 +73,12 @@ def header_structs():
             line = line.strip()
             if not line:
                 continue
+            arr = re.search(r"\[(\d+)\]\s*$", line)  # a member array is [T; N], not a pointer
+            if arr:
+                line = line[:arr.start()]
             fname = re.findall(r"[A-Za-z_][A-Za-z0-9_]*", line)[-1]
-            fields.append((fname, rust_of(*c_type(line))))
+            ty = rust_of(*c_type(line))
+            fields.append((fname, f"[{ty}; {arr.group(1)}]" if arr else ty))
         out[STRUCTS[name]] = fields
     return out
 
@@ -107,7 +112,7 @@ def generate():
         for f, t in fields:
             lines.append(f"    pub {f}: {t},")
         lines.append("}")
-    for opaque in ("PktCtx", "PktGen", "PktMgpu", "PktPcapStream"):
+    for opaque in ("PktCtx", "PktGen", "PktMgpu", "PktPcapStream", "PktFlowTable"):
         lines.append(f"#[repr(C)] pub struct {opaque} {{ _p: [u8; 0] }}")
     lines += ["", '#[link(name = "pktgpu")]', 'extern "C" {']
     for name, (args, ret) in fn.items():
