@@ -269,6 +269,27 @@ class Parser {
               ctx_, "pkt_flow_key_batch");
     }
 
+    // A first-match rule table (pkt_match_create): rule r is the AND of terms [first_term, first_term + nterms),
+    // a packet takes the action of the lowest rule that matches it, else default_action.  The caller destroys
+    // it with pkt_match_destroy after the calls queued on it.
+    pkt_match_t* match_program(const std::vector<pkt_match_term_t>& terms, const std::vector<pkt_match_rule_t>& rules,
+                               uint32_t default_action = 0) {
+        pkt_match_t* m = nullptr;
+        check(pkt_match_create(ctx_, terms.data(), (uint32_t)terms.size(), rules.data(), (uint32_t)rules.size(),
+                               default_action, &m),
+              ctx_, "pkt_match_create");
+        return m;
+    }
+
+    // The program over a parsed device batch (pkt_match_batch), one pass: rule / action / select / matched are
+    // device arrays of n, hits / bytes device uint64_t[nrules + 1] that are added to; each may be NULL.
+    // `select` is what pcap_write and edit take.  Asynchronous on `s`.
+    void match(pkt_match_t* m, const pkt_batch_t& b, const pkt_chain_t& chain, uint8_t* select, uint8_t* rule = nullptr,
+               uint32_t* action = nullptr, uint64_t* matched = nullptr, uint64_t* hits = nullptr,
+               uint64_t* bytes = nullptr, hipStream_t s = nullptr) {
+        check(pkt_match_batch(m, &b, &chain, rule, action, select, matched, hits, bytes, s), ctx_, "pkt_match_batch");
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

@@ -851,6 +851,82 @@ int pkt_flow_table_clear(pkt_flow_table_t *table, void *stream);
 int pkt_flow_table_destroy(pkt_flow_table_t *table);
 const char *pkt_flow_table_last_error(const pkt_flow_table_t *table);
 
+/* ---- first-match rule tables over a parsed batch ----
+ * Which packets a consumer keeps: the producer of the `select` mask that pkt_pcap_write and pkt_edit_batch
+ * take, and the classifier beside the flow table.  The reference defines nothing here, so this header fixes the
+ * semantics.  A program is up to PKT_MATCH_MAX_RULES rules over up to PKT_MATCH_MAX_TERMS terms; it is compiled
+ * and uploaded once (pkt_match_create) and evaluated by one kernel in a single pass over the packets' bytes.
+ *  - batch / chain: any pkt_batch_t under its usual slab rules, with the chain columns of a parse of it, of a
+ *    stream's columns over pkt_pcap_stream_batch, or pkt_edit_batch's out_chain.  `len` is the packet's length
+ *    under the pkt_batch_t clamp rules (clamped to the slab end and to 65535); n_hdrs is taken as
+ *    min(n_hdrs, PKT_MAX_HDRS).  Whatever the columns hold, no byte outside the packet is used.
+ *  - A term's header is the `occurrence`-th list entry of `hdr_type` (0 = first), counted as
+ *    pkt_extract_fields counts.  It is PRESENT iff such an entry exists and hdr_off + pkt_hdr_size(hdr_type)
+ *    <= len.  v = bits [start..=end], MSB-first from the header's first byte: pkt_extract_fields' value;
+ *    width 1..64.
+ *  - PKT_MATCH_HAS: raw = present (start, end, a, b ignored).  PKT_MATCH_EQ: raw = present and
+ *    ((v ^ a) & b & widthmask) == 0, so a mask of 0 is true whenever the header is present.  PKT_MATCH_RANGE:
+ *    raw = present and a <= v <= b, unsigned; a > b is allowed and never true.  PKT_MATCH_LEN: raw = a <= len
+ *    <= b; its `field` must be all zero.  A term's result is raw ^ PKT_MATCH_NOT, so NOT on an absent header
+ *    is true.  An IPv6 address is two 64-bit terms, a /64 prefix one.
+ *  - Rule r matches iff all its terms [first_term, first_term + nterms) are true; a rule with nterms == 0
+ *    matches every packet (n_hdrs == 0 included).  The rules' ranges may overlap or share terms.
+ *  - matched[i]: bit r set iff rule r matches.  rule[i]: the lowest matching r, else PKT_MATCH_NONE.
+ *    action[i]: that rule's action, else default_action.  select[i] = action[i] != 0: exactly what
+ *    pkt_pcap_write and pkt_edit_batch take.  rule / action / select / matched: device [n], each may be NULL.
+ *  - hits / bytes: device uint64_t[nrules + 1], 8-byte aligned, caller-owned, each may be NULL.  They are ADDED
+ *    to: the caller zeroes them once and they accumulate across batches and stream windows.  hits[rule[i]] +=
+ *    1, bytes[rule[i]] += len, index nrules standing for "none".  Integer atomics, exact: every call adds
+ *    exactly n to sum(hits).  With all six outputs NULL the call succeeds and launches nothing.
+ *  - pkt_match_create validates, compiles and uploads the program; blocking, and the only allocation (the
+ *    pkt_gen_create pattern).  PKT_ERR_INVALID_ARG with a text in pkt_ctx_last_error: nrules > 64 or nterms >
+ *    256; a rule range that runs past nterms; an unknown op or flag bit; non-zero reserved fields; a non-LEN
+ *    term with hdr_type outside 1..21, end < start, end >= 8 * pkt_hdr_size(hdr_type) or a width above 64
+ *    (HAS ignores the bits but still needs a valid type); a LEN term with a non-zero `field`; a NULL pointer
+ *    with a non-zero count.  nrules == 0 is legal: every packet gets default_action.
+ *  - pkt_match_batch is asynchronous on `stream`, keeps no ctx state and never writes the program: several
+ *    calls on one program may be in flight on different streams.  PKT_ERR_INVALID_ARG before any launch (the
+ *    text: pkt_ctx_last_error of the ctx the program was created on): the batch and slab rules, a NULL chain or,
+ *    with n > 0, chain column, n >= 2^32, a matched, hits or bytes that is not 8-byte aligned.  n == 0
+ *    succeeds, launches nothing and leaves the counters untouched.  pkt_match_destroy is the caller's to order
+ *    after the queued calls.
+ *  - On the device a lane owns a packet: its window and chain are loaded once whatever the number of rules,
+ *    the compiled program is read through uniform (scalar) loads, each distinct (hdr_type, occurrence) is
+ *    resolved once per packet, a block merges its counts in LDS and adds once per non-zero (rule, counter).
+ *    No lane waits for another.
+ * pkt_match_host is the same operation on HOST pointers, straight from the terms and rules: no ctx, no device. */
+#define PKT_MATCH_MAX_RULES 64
+#define PKT_MATCH_MAX_TERMS 256
+#define PKT_MATCH_NONE      0xFFu      /* rule[i] when no rule matched */
+#define PKT_MATCH_NOT       1u         /* term flag: invert the term */
+typedef enum pkt_match_op { PKT_MATCH_HAS = 0, PKT_MATCH_EQ = 1, PKT_MATCH_RANGE = 2, PKT_MATCH_LEN = 3 } pkt_match_op_t;
+typedef struct pkt_match_term {        /* 32 bytes */
+    pkt_field_spec_t field;            /* header type, occurrence, bits [start..=end] as pkt_extract_fields */
+    uint8_t  op;                       /* pkt_match_op_t */
+    uint8_t  flags;                    /* PKT_MATCH_NOT or 0 */
+    uint16_t reserved;                 /* 0 */
+    uint32_t reserved2;                /* 0 */
+    uint64_t a;                        /* EQ: value.  RANGE / LEN: lo */
+    uint64_t b;                        /* EQ: mask.   RANGE / LEN: hi, inclusive */
+} pkt_match_term_t;
+typedef struct pkt_match_rule {        /* 8 bytes */
+    uint16_t first_term;               /* the rule is the AND of terms [first_term, first_term + nterms) */
+    uint16_t nterms;
+    uint32_t action;                   /* caller-defined; 0 means "not selected" */
+} pkt_match_rule_t;
+typedef struct pkt_match pkt_match_t;
+size_t pkt_sizeof_match_term(void);
+size_t pkt_sizeof_match_rule(void);
+int pkt_match_create(pkt_ctx_t *ctx, const pkt_match_term_t *terms, uint32_t nterms,
+                     const pkt_match_rule_t *rules, uint32_t nrules, uint32_t default_action, pkt_match_t **m);
+int pkt_match_destroy(pkt_match_t *m);
+int pkt_match_batch(pkt_match_t *m, const pkt_batch_t *batch, const pkt_chain_t *chain,
+                    uint8_t *rule, uint32_t *action, uint8_t *select, uint64_t *matched,
+                    uint64_t *hits, uint64_t *bytes, void *stream);
+int pkt_match_host(const pkt_match_term_t *terms, uint32_t nterms, const pkt_match_rule_t *rules, uint32_t nrules,
+                   uint32_t default_action, const pkt_batch_t *batch, const pkt_chain_t *chain,
+                   uint8_t *rule, uint32_t *action, uint8_t *select, uint64_t *matched, uint64_t *hits, uint64_t *bytes);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -6,6 +6,7 @@
 #include "../../include/pktgpu.h"
 #include "pktgpu_batch.hpp"
 #include "pktgpu_flow.hpp"
+#include "pktgpu_match.hpp"
 
 namespace {
 
@@ -673,6 +674,68 @@ int pkt_flow_table_destroy(pkt_flow_table_t* t) {
 }
 
 const char* pkt_flow_table_last_error(const pkt_flow_table_t* t) { return t ? t->err.c_str() : "null table"; }
+
+// ---- pkt_match_batch on host pointers (the CPU model of pktgpu_match.hip), straight from the source terms and
+// rules: every rule, every term, byte by byte.
+size_t pkt_sizeof_match_term(void) { return sizeof(pkt_match_term_t); }
+size_t pkt_sizeof_match_rule(void) { return sizeof(pkt_match_rule_t); }
+
+int pkt_match_host(const pkt_match_term_t* terms, uint32_t nterms, const pkt_match_rule_t* rules, uint32_t nrules,
+                   uint32_t default_action, const pkt_batch_t* b, const pkt_chain_t* chain, uint8_t* rule,
+                   uint32_t* action, uint8_t* select, uint64_t* matched, uint64_t* hits, uint64_t* bytes) {
+    if (match_program_error(terms, nterms, rules, nrules)) return PKT_ERR_INVALID_ARG;
+    if (!b || !chain) return PKT_ERR_INVALID_ARG;
+    if (b->n >= (1ull << 32)) return PKT_ERR_INVALID_ARG;
+    if (((uintptr_t)matched | (uintptr_t)hits | (uintptr_t)bytes) & 7) return PKT_ERR_INVALID_ARG;
+    const uint64_t n = b->n;
+    if (n == 0) return PKT_SUCCESS;
+    if (bad_batch(b) || !chain->n_hdrs || !chain->hdr_type || !chain->hdr_off) return PKT_ERR_INVALID_ARG;
+    const BatchSrc src = batch_src(b);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t off = pkt_off(src, i);
+        const uint32_t len = pkt_len(src, i, off);
+        const uint8_t* p = b->slab + off;
+        uint32_t nh = chain->n_hdrs[i];
+        nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+        uint64_t bits = 0;
+        for (uint32_t r = 0; r < nrules; r++) {
+            bool all = true;
+            for (uint32_t k = 0; k < rules[r].nterms && all; k++) {
+                const pkt_match_term_t& m = terms[rules[r].first_term + k];
+                bool raw;
+                if (m.op == PKT_MATCH_LEN) {
+                    raw = m.a <= len && len <= m.b;
+                } else {
+                    int64_t ho = -1;
+                    for (uint32_t j = 0, c = 0; j < nh; j++)
+                        if (chain->hdr_type[j * n + i] == m.field.hdr_type && c++ == m.field.occurrence) {
+                            ho = chain->hdr_off[j * n + i];
+                            break;
+                        }
+                    raw = ho >= 0 && (uint64_t)ho + kHdrs[m.field.hdr_type].size <= len;
+                    if (raw && m.op != PKT_MATCH_HAS) {
+                        uint64_t v = 0;  // bits [start..=end], MSB first (width <= 64)
+                        for (uint32_t q = m.field.start; q <= m.field.end; q++)
+                            v = v << 1 | ((p[ho + (q >> 3)] >> (7 - (q & 7))) & 1u);
+                        const uint64_t wm = match_width_mask(m.field.end - m.field.start + 1u);
+                        raw = m.op == PKT_MATCH_EQ ? ((v ^ m.a) & m.b & wm) == 0 : (m.a <= v && v <= m.b);
+                    }
+                }
+                all = raw != ((m.flags & PKT_MATCH_NOT) != 0);
+            }
+            if (all) bits |= 1ull << r;
+        }
+        const uint32_t first = bits ? (uint32_t)__builtin_ctzll(bits) : PKT_MATCH_NONE;
+        const uint32_t act = bits ? rules[first].action : default_action;
+        if (rule) rule[i] = (uint8_t)first;
+        if (action) action[i] = act;
+        if (select) select[i] = act != 0;
+        if (matched) matched[i] = bits;
+        if (hits) hits[bits ? first : nrules] += 1;
+        if (bytes) bytes[bits ? first : nrules] += len;
+    }
+    return PKT_SUCCESS;
+}
 
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,
 // packet.rs:724-731: insert / set_payload).

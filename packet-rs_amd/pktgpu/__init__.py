@@ -25,7 +25,7 @@ from . import schema
 from .schema import (ABI_VERSION, DEPTH_LIMIT, ENTRIES, ENTRY_ID, GROUPS, HDR_ID, HDR_NAMES,  # noqa: F401
                      HDR_SIZES, MAX_HDRS, OK, STATUS_NAMES, TRUNCATED)
 
-__all__ = ["Parser", "FlowTable", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
+__all__ = ["Parser", "FlowTable", "MatchProgram", "match", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
 
 
 def resolve_columns(columns):
@@ -696,6 +696,43 @@ class Parser:
             del res["rss"]
         return res
 
+    def match_program(self, rules, default=0):
+        """pkt_match_create: compile and upload a first-match rule table -> MatchProgram.  `rules`: a list of
+        (action, [term, ...]), a rule being the AND of its terms and action 0 meaning "not selected".  A term is
+        (hdr, occurrence, field, op, a[, b]) with hdr a header name or id, field a name from pktgpu.fields or a
+        (start, end) bit pair (None for "has"), op one of "has", "not has", "==", "!=", "in", "not in"; for
+        "==" / "!=" `a` is the value and the optional `b` a mask (default: all ones), for "in" / "not in" a..b
+        is the inclusive range.  ("len", "in" | "not in", lo, hi) tests the packet's length.  `default`: the
+        action of a packet no rule matches.  (A (PktMatchTerm array, PktMatchRule array) pair is taken as it
+        is: rules that share or overlap their terms.)"""
+        return MatchProgram(self, rules, default)
+
+    def match(self, slab, chain, prog, stride=None, n=None, offsets=None, lens=None,
+              outputs=("rule", "action", "select", "matched"), hits=None, bytes=None, stream=None):
+        """pkt_match_batch: evaluate a MatchProgram over a parsed batch in one pass -> a dict of device tensors,
+        the `outputs` asked for among "rule" (uint8: the first matching rule, pktgpu.MATCH_NONE = none),
+        "action" (uint32), "select" (uint8: action != 0, what pcap_write and edit take) and "matched" (uint64:
+        bit r = rule r matches).  hits / bytes: True allocates zeroed uint64 [nrules + 1] counters and returns
+        them; a tensor passed in is accumulated into (index nrules = no rule).  `chain`: the chain columns of
+        a parse of the batch, a stream's columns over its batch(), or edit's out chain.  Asynchronous on
+        `stream`."""
+        torch = _torch()
+        b = self._batch(slab, n, stride, offsets, lens)
+        ch = self._chain(chain)
+        dts = {"rule": torch.uint8, "action": torch.uint32, "select": torch.uint8, "matched": torch.uint64}
+        res = {k: torch.empty(b.n, dtype=dts[k], device=self.torch_device) for k in outputs}
+        for name, c in (("hits", hits), ("bytes", bytes)):
+            if c is True:
+                c = torch.zeros(prog.nrules + 1, dtype=torch.uint64, device=self.torch_device)
+            if c is not None and c is not False:
+                assert c.dtype == torch.uint64 and c.numel() == prog.nrules + 1 and c.is_contiguous()
+                res[name] = c
+        ptr = lambda k: res[k].data_ptr() if k in res and res[k].numel() else None  # noqa: E731
+        self._check(self._L.pkt_match_batch(prog._m, ctypes.byref(b), ctypes.byref(ch), ptr("rule"), ptr("action"),
+                                            ptr("select"), ptr("matched"), ptr("hits"), ptr("bytes"),
+                                            self._stream(stream)), "pkt_match_batch")
+        return res
+
     def pcap_index_device_timed(self, buf, offsets, lens, stream=None):
         """pkt_pcap_index_device_timed into the caller's device `offsets` / `lens` (cap = their
         length): (record count, [guess, scan, emit] kernel ms from HIP events between them)."""
@@ -991,6 +1028,109 @@ def flow_keys(slab, chain, which_ip=FLOW_LAST, symmetric=False, ports=True, seed
                              ptr(res["hash"]), ptr(res.get("rss")), ptr(res["dir"]), ptr(res["plen"]), ptr(res["status"]))
     if rc != 0:
         raise ValueError(f"pkt_flow_key_host failed ({rc})")
+    return res
+
+
+MATCH_NONE = schema.MATCH_NONE
+_MATCH_OPS = {"has": (schema.MATCH_HAS, 0), "not has": (schema.MATCH_HAS, schema.MATCH_NOT),
+              "==": (schema.MATCH_EQ, 0), "!=": (schema.MATCH_EQ, schema.MATCH_NOT),
+              "in": (schema.MATCH_RANGE, 0), "not in": (schema.MATCH_RANGE, schema.MATCH_NOT)}
+
+
+def match_term(term):
+    """One term of a match program as a PktMatchTerm (Parser.match_program's term forms; a PktMatchTerm is
+    returned as it is)."""
+    from . import _lib, fields
+    if isinstance(term, _lib.PktMatchTerm):
+        return term
+    U64 = (1 << 64) - 1
+    if term[0] == "len":
+        _, op, lo, hi = term
+        if op not in ("in", "not in"):
+            raise ValueError(f"len term: op {op!r} is neither 'in' nor 'not in'")
+        return _lib.PktMatchTerm(_lib.PktFieldSpec(), schema.MATCH_LEN, _MATCH_OPS[op][1], 0, 0, int(lo) & U64, int(hi) & U64)
+    hdr, occ, field, op = term[:4]
+    if op not in _MATCH_OPS:
+        raise ValueError(f"unknown match op {op!r}")
+    t = HDR_ID[hdr] if isinstance(hdr, str) else int(hdr)
+    kind, flags = _MATCH_OPS[op]
+    if kind == schema.MATCH_HAS:
+        start = end = a = b = 0
+    else:
+        start, end = fields.FIELDS[t][field] if isinstance(field, str) else field
+        a = int(term[4])
+        if kind == schema.MATCH_EQ:
+            b = int(term[5]) if len(term) > 5 else U64
+        else:
+            b = int(term[5])
+    return _lib.PktMatchTerm(_lib.PktFieldSpec(t, int(occ), int(start), int(end), 0), kind, flags, 0, 0, a & U64, b & U64)
+
+
+def match_arrays(rules):
+    """(PktMatchTerm array, nterms, PktMatchRule array, nrules) of Parser.match_program's `rules`: each rule's
+    terms laid out one run after the other.  A (term array, rule array) pair passes through."""
+    from . import _lib
+    if isinstance(rules, tuple) and len(rules) == 2 and isinstance(rules[1], ctypes.Array):
+        return rules[0], len(rules[0]) if rules[0] is not None else 0, rules[1], len(rules[1])
+    terms, rr = [], []
+    for action, tl in rules:
+        rr.append((len(terms), len(tl), int(action)))
+        terms.extend(match_term(t) for t in tl)
+    ta = (_lib.PktMatchTerm * max(1, len(terms)))(*terms)
+    ra = (_lib.PktMatchRule * max(1, len(rr)))(*[_lib.PktMatchRule(*r) for r in rr])
+    return ta, len(terms), ra, len(rr)
+
+
+class MatchProgram:
+    """pkt_match_t: a compiled first-match rule table on a parser's device (Parser.match_program)."""
+
+    def __init__(self, parser, rules, default=0):
+        self.parser = parser
+        self._L = parser._L
+        ta, self.nterms, ra, self.nrules = match_arrays(rules)
+        self.default = int(default)
+        h = ctypes.c_void_p()
+        parser._check(self._L.pkt_match_create(parser._ctx, ta, self.nterms, ra, self.nrules, self.default,
+                                               ctypes.byref(h)), "pkt_match_create")
+        self._m = h
+
+    def close(self):
+        if getattr(self, "_m", None):
+            self._L.pkt_match_destroy(self._m)
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def match(slab, chain, rules, default=0, stride=None, n=None, offsets=None, lens=None,
+          outputs=("rule", "action", "select", "matched"), hits=None, bytes=None):
+    """pkt_match_host over numpy arrays (no device): Parser.match's arguments with numpy arrays and the rules
+    themselves in place of a MatchProgram -> the same dict of numpy arrays.  hits / bytes: True allocates zeroed
+    uint64 [nrules + 1] counters; an array passed in (uint64, C-contiguous) is accumulated into."""
+    from . import _lib
+    L = _lib.load()
+    ta, nterms, ra, nrules = match_arrays(rules)
+    b, keep = _host_batch(_lib, dict(slab=slab, stride=stride, n=n, offsets=offsets, lens=lens))
+    cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+            np.ascontiguousarray(chain["hdr_off"], np.uint16))
+    ch = _lib.PktChain(*[c.ctypes.data for c in cols])
+    dts = {"rule": np.uint8, "action": np.uint32, "select": np.uint8, "matched": np.uint64}
+    res = {k: np.zeros(b.n, dts[k]) for k in outputs}
+    for name, c in (("hits", hits), ("bytes", bytes)):
+        if c is True:
+            c = np.zeros(nrules + 1, np.uint64)
+        if c is not None and c is not False:
+            assert c.dtype == np.uint64 and c.size == nrules + 1 and c.flags.c_contiguous
+            res[name] = c
+    ptr = lambda k: res[k].ctypes.data if k in res and res[k].size else None  # noqa: E731
+    rc = L.pkt_match_host(ta, nterms, ra, nrules, int(default), ctypes.byref(b), ctypes.byref(ch), ptr("rule"),
+                          ptr("action"), ptr("select"), ptr("matched"), ptr("hits"), ptr("bytes"))
+    if rc != 0:
+        raise ValueError(f"pkt_match_host failed ({rc})")
     return res
 
 

@@ -68,6 +68,16 @@ class PktFlowRecord(ctypes.Structure):
                 ("bytes", ctypes.c_uint64 * 2)]
 
 
+class PktMatchTerm(ctypes.Structure):
+    _fields_ = [("field", PktFieldSpec), ("op", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16), ("reserved2", ctypes.c_uint32), ("a", ctypes.c_uint64),
+                ("b", ctypes.c_uint64)]
+
+
+class PktMatchRule(ctypes.Structure):
+    _fields_ = [("first_term", ctypes.c_uint16), ("nterms", ctypes.c_uint16), ("action", ctypes.c_uint32)]
+
+
 # Every function declared in include/pktgpu.h: name -> (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -185,6 +195,16 @@ SIGNATURES = {
     "pkt_flow_table_clear": (ctypes.c_int, [_P, _P]),
     "pkt_flow_table_destroy": (ctypes.c_int, [_P]),
     "pkt_flow_table_last_error": (ctypes.c_char_p, [_P]),
+    "pkt_sizeof_match_term": (ctypes.c_size_t, []),
+    "pkt_sizeof_match_rule": (ctypes.c_size_t, []),
+    "pkt_match_create": (ctypes.c_int, [_P, ctypes.POINTER(PktMatchTerm), ctypes.c_uint32, ctypes.POINTER(PktMatchRule),
+                                        ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "pkt_match_destroy": (ctypes.c_int, [_P]),
+    "pkt_match_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), _P, _P, _P, _P, _P, _P,
+                                       _P]),
+    "pkt_match_host": (ctypes.c_int, [ctypes.POINTER(PktMatchTerm), ctypes.c_uint32, ctypes.POINTER(PktMatchRule),
+                                      ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(PktBatch),
+                                      ctypes.POINTER(PktChain), _P, _P, _P, _P, _P, _P]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -264,7 +284,9 @@ def load():
             or L.pkt_sizeof_cmp_summary() != ctypes.sizeof(PktCmpSummary) \
             or L.pkt_sizeof_edit_op() != ctypes.sizeof(PktEditOp) \
             or L.pkt_sizeof_flow_key() != ctypes.sizeof(PktFlowKey) \
-            or L.pkt_sizeof_flow_record() != ctypes.sizeof(PktFlowRecord):
+            or L.pkt_sizeof_flow_record() != ctypes.sizeof(PktFlowRecord) \
+            or L.pkt_sizeof_match_term() != ctypes.sizeof(PktMatchTerm) \
+            or L.pkt_sizeof_match_rule() != ctypes.sizeof(PktMatchRule):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L
     return L

@@ -28,6 +28,14 @@ FLOW_SYMMETRIC, FLOW_NO_PORTS = 1, 2
 FLOW_UPD_OK, FLOW_UPD_SKIPPED, FLOW_UPD_COLLISION, FLOW_UPD_FULL = range(4)
 FLOW_UPD_STATUS = ["OK", "SKIPPED", "COLLISION", "FULL"]
 FLOW_NONE = 0xFFFFFFFF  # flow_id of a packet that is not FLOW_UPD_OK
+
+# pkt_match_* (first-match rule tables)
+MATCH_MAX_RULES, MATCH_MAX_TERMS = 64, 256
+MATCH_NONE = 0xFF  # rule[i] when no rule matched
+MATCH_NOT = 1      # term flag: invert the term
+MATCH_HAS, MATCH_EQ, MATCH_RANGE, MATCH_LEN = range(4)
+MATCH_OPS = ["HAS", "EQ", "RANGE", "LEN"]
+
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
                            ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])

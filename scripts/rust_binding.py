@@ -19,10 +19,12 @@ C_SCALARS = {"uint8_t": "u8", "uint16_t": "u16", "uint32_t": "u32", "uint64_t": 
              "pkt_field_spec_t": "PktFieldSpec", "pkt_gen_field_t": "PktGenField", "pkt_gen_t": "PktGen",
              "pkt_mgpu_t": "PktMgpu", "pkt_gather_piece_t": "PktGatherPiece", "pkt_pcap_stream_t": "PktPcapStream",
              "pkt_cmp_summary_t": "PktCmpSummary", "pkt_edit_op_t": "PktEditOp", "pkt_flow_key_t": "PktFlowKey",
-             "pkt_flow_record_t": "PktFlowRecord", "pkt_flow_table_t": "PktFlowTable"}
+             "pkt_flow_record_t": "PktFlowRecord", "pkt_flow_table_t": "PktFlowTable",
+             "pkt_match_term_t": "PktMatchTerm", "pkt_match_rule_t": "PktMatchRule", "pkt_match_t": "PktMatch"}
 STRUCTS = {"pkt_batch": "PktBatch", "pkt_out": "PktOut", "pkt_field_spec": "PktFieldSpec", "pkt_chain": "PktChain",
            "pkt_gen_field": "PktGenField", "pkt_gather_piece": "PktGatherPiece", "pkt_cmp_summary": "PktCmpSummary",
-           "pkt_edit_op": "PktEditOp", "pkt_flow_key": "PktFlowKey", "pkt_flow_record": "PktFlowRecord"}
+           "pkt_edit_op": "PktEditOp", "pkt_flow_key": "PktFlowKey", "pkt_flow_record": "PktFlowRecord",
+           "pkt_match_term": "PktMatchTerm", "pkt_match_rule": "PktMatchRule"}
 
 
 def _strip(src):
@@ -112,7 +114,7 @@ def generate():
         for f, t in fields:
             lines.append(f"    pub {f}: {t},")
         lines.append("}")
-    for opaque in ("PktCtx", "PktGen", "PktMgpu", "PktPcapStream", "PktFlowTable"):
+    for opaque in ("PktCtx", "PktGen", "PktMgpu", "PktPcapStream", "PktFlowTable", "PktMatch"):
         lines.append(f"#[repr(C)] pub struct {opaque} {{ _p: [u8; 0] }}")
     lines += ["", '#[link(name = "pktgpu")]', 'extern "C" {']
     for name, (args, ret) in fn.items():
@@ -152,7 +154,8 @@ def update_integration():
     md = open(p).read()
     a = md.index("```rust\n") + len("```rust\n")
     b = md.index("\n// ---- safe-ish helpers", a)
-    open(p, "w").write(md[:a] + generate() + "\n" + md[b:])
+    new = md[:a] + generate() + "\n" + md[b:]  # (generated before the file is opened for writing)
+    open(p, "w").write(new)
 
 
 if __name__ == "__main__":
