@@ -290,6 +290,48 @@ class Parser {
         check(pkt_match_batch(m, &b, &chain, rule, action, select, matched, hits, bytes, s), ctx_, "pkt_match_batch");
     }
 
+    // A stable partition of up to max_n packets into nbuckets (1..256) queues (pkt_dispatch_create).  An empty
+    // `table` is DIRECT mode (bucket = key when key < nbuckets, else dropped); otherwise it is the RSS indirection
+    // table (a power-of-two length up to 4096, entries < nbuckets or PKT_DISPATCH_DROP): bucket = table[key &
+    // (len - 1)].  The caller destroys it with pkt_dispatch_destroy after the calls queued on it.
+    pkt_dispatch_t* dispatcher(uint32_t nbuckets, const std::vector<uint16_t>& table, uint64_t max_n) {
+        pkt_dispatch_t* d = nullptr;
+        check(pkt_dispatch_create(ctx_, nbuckets, table.empty() ? nullptr : table.data(), (uint32_t)table.size(), max_n, &d),
+              ctx_, "pkt_dispatch_create");
+        return d;
+    }
+
+    // The partition of n packets by `key` (pkt_dispatch_batch): perm[pos] = source index (buckets in order, source
+    // order within a bucket, the dropped last), rank its inverse, bucket[i] the packet's bucket, start (device
+    // uint64_t[nbuckets + 2]) the buckets' first positions.  Each may be NULL.  One call at a time per handle.
+    // Asynchronous on `s`.
+    void dispatch(pkt_dispatch_t* d, const uint32_t* key, uint64_t n, uint32_t* perm, uint64_t* start,
+                  uint32_t* rank = nullptr, uint16_t* bucket = nullptr, const uint8_t* select = nullptr,
+                  hipStream_t s = nullptr) {
+        check(pkt_dispatch_batch(d, key, select, n, bucket, perm, rank, start, s), ctx_, "pkt_dispatch_batch");
+    }
+
+    // Packets and columns gathered by `perm` (pkt_reorder_batch): position k takes packet perm[k] into dst + k *
+    // slot (out_len[k] = min(length, slot)) and every column that `cols` and `out_cols` both hold.  With seg_start
+    // (dispatch's start) and nseg segments the slot columns are laid out per segment, so that segment s is the batch
+    // segment(...) below, and positions at or past seg_start[nseg] are not written.  Asynchronous on `s`.
+    void reorder(const pkt_batch_t& b, const uint32_t* perm, uint64_t m, uint8_t* dst, uint64_t dst_len, uint32_t slot,
+                 uint32_t* out_len, const pkt_out_t* cols = nullptr, const pkt_out_t* out_cols = nullptr,
+                 const uint64_t* seg_start = nullptr, uint32_t nseg = 0, hipStream_t s = nullptr) {
+        check(pkt_reorder_batch(ctx_, &b, cols, perm, m, seg_start, nseg, dst, dst_len, slot, out_len, out_cols, s), ctx_,
+              "pkt_reorder_batch");
+    }
+
+    // Segment [s0, s1) (two consecutive values of a HOST copy of dispatch's start) of a segmented reorder as a
+    // batch of its own, and its chain in *chain (when the three chain columns were gathered into out_cols).
+    static pkt_batch_t segment(uint8_t* dst, uint32_t slot, const uint32_t* out_len, uint64_t s0, uint64_t s1,
+                               const pkt_out_t* out_cols = nullptr, pkt_chain_t* chain = nullptr) {
+        if (out_cols && chain)
+            *chain = pkt_chain_t{out_cols->n_hdrs + s0, out_cols->hdr_type + PKT_MAX_HDRS * s0,
+                                 out_cols->hdr_off + PKT_MAX_HDRS * s0};
+        return pkt_batch_t{dst + s0 * slot, (s1 - s0) * slot, nullptr, out_len + s0, slot, 0, s1 - s0};
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

@@ -927,6 +927,93 @@ int pkt_match_host(const pkt_match_term_t *terms, uint32_t nterms, const pkt_mat
                    uint32_t default_action, const pkt_batch_t *batch, const pkt_chain_t *chain,
                    uint8_t *rule, uint32_t *action, uint8_t *select, uint64_t *matched, uint64_t *hits, uint64_t *bytes);
 
+/* ---- per-queue batches: a stable bucket partition and the gather that follows it ----
+ * What an RSS hash exists for: hand each packet of a device batch to one of N queues, workers or GPUs, in one pass
+ * over the bytes.  pkt_dispatch_batch partitions n packets into buckets by a 32-bit key (pkt_flow_key_batch's rss,
+ * pkt_match_batch's action or rule, a shard number); pkt_reorder_batch gathers packets and columns by the
+ * resulting permutation into per-bucket batches every pkt_*_batch call accepts.  The reference defines nothing
+ * here, so this header fixes the semantics; the one outside convention is the RSS indirection table,
+ * queue = table[hash & (len - 1)].
+ *
+ * pkt_dispatch_create: blocking, and the only allocation (the pkt_match_create pattern); the handle owns the
+ * scratch for max_n packets.  nbuckets in 1..PKT_DISPATCH_MAX_BUCKETS; `table` is HOST memory, captured at the
+ * call: NULL selects DIRECT mode, otherwise table_len is a power of two in 1..PKT_DISPATCH_MAX_TABLE and every
+ * entry is < nbuckets or PKT_DISPATCH_DROP; max_n in 1..2^32-1.  A violation is PKT_ERR_INVALID_ARG with a text
+ * starting "pkt_dispatch" in pkt_ctx_last_error.
+ *  - The bucket b_i of packet i: PKT_DISPATCH_DROP if `select` is non-NULL and select[i] == 0; in DIRECT mode
+ *    key[i] < nbuckets ? key[i] : PKT_DISPATCH_DROP; in table mode table[key[i] & (table_len - 1)].
+ *  - Order: packets are ordered by (b'_i, i) with b' = nbuckets for DROP, so the partition is stable (source
+ *    order is kept within a bucket) and the dropped packets form the tail.  perm[pos] = i and rank[i] = pos
+ *    (device uint32_t[n]); bucket[i] = b_i (device uint16_t[n], DROP as 0xFFFF); start: device
+ *    uint64_t[nbuckets + 2], 8-byte aligned, start[b] = the number of packets with b' < b, so start[0] = 0,
+ *    start[nbuckets] = the kept count and start[nbuckets + 1] = n.  start is written, not added to.  All results
+ *    are exact and the same from run to run.
+ *  - Every output may be NULL; with all four NULL nothing is launched.  key (device uint32_t[n]) is required when
+ *    n > 0.  For n == 0, start (if given) is zero-filled on the stream and nothing else happens.  n > max_n,
+ *    n >= 2^32 or a misaligned start is PKT_ERR_INVALID_ARG before any launch (the text: pkt_ctx_last_error of the
+ *    ctx the handle was created on).  Asynchronous on `stream`; one call at a time per handle (the calls share
+ *    its scratch), as for pkt_flow_table.  pkt_dispatch_destroy is the caller's to order after the queued calls.
+ *  - On the device three launches whose boundaries publish the data (no lane waits for another, no global
+ *    atomics): each tile of 2048 packets counts its buckets; one exclusive scan over the [bucket][tile] counts
+ *    gives every tile's first position in every bucket, and start; each tile then ranks its packets again, within
+ *    a wave by ballots over the bucket's bits, and stores perm, rank and bucket.
+ * pkt_dispatch_host is the same operation on HOST pointers: no ctx, no device, no handle.
+ *
+ * pkt_reorder_batch: position k < m takes source packet p = perm[k] (`perm`: device uint32_t[m], pkt_dispatch_
+ * batch's perm or any index list).  p >= batch->n is an EMPTY position: out_len = 0, every gathered column 0, no
+ * packet byte written.  Whatever perm and the columns hold, no byte outside the source packets is used and none
+ * outside what is listed here is written.
+ *  - Bytes (dst != NULL): dst is 16-byte aligned, `slot` a multiple of 16 and at least 16, dst_len >= m * slot.
+ *    out_len[k] = min(len_p, slot) with len_p the packet's length under the pkt_batch_t clamp rules: the cut is
+ *    pkt_pcap_write's snaplen, not an error.  Exactly bytes [k*slot, k*slot + round_up(out_len[k], 16)) of dst
+ *    are written, the packet's bytes, then zeros; the rest of the slot is not written and dst is never read.  The
+ *    source is any pkt_batch_t under its usual slab rules, its packets at any alignment; it must not overlap dst.
+ *    out_len (device uint32_t[m]) may be NULL.  dst == NULL means columns only; out_len must then be NULL.
+ *  - Columns: column c (any of pkt_out_t's 49) is gathered iff cols->c and out_cols->c are both non-NULL;
+ *    out_cols->c without cols->c is PKT_ERR_INVALID_ARG; either struct may be NULL (no columns).  Input slot
+ *    columns are strided by batch->n.  A per-packet column writes element k.  With nseg == 0 the slot columns are
+ *    written as [PKT_MAX_HDRS][m].
+ *  - Segments: seg_start is a device uint64_t[nseg + 1] holding what pkt_dispatch_batch's `start` holds, nseg <=
+ *    257; the caller promises it is non-decreasing from 0; its values are clamped to m.  Segment s is positions
+ *    [seg_start[s], seg_start[s+1]) and n_s its size; row j of a slot column lies at element PKT_MAX_HDRS *
+ *    seg_start[s] + j * n_s + (k - seg_start[s]).  Positions at or past seg_start[nseg] are not written at all
+ *    (no bytes, no out_len, no columns): with m = n and nseg = nbuckets this skips the dropped tail.
+ *  - Slot rows: when cols->n_hdrs is given only rows j < min(n_hdrs[p], PKT_MAX_HDRS) are written, as a parse
+ *    leaves the later ones; without it, and for an empty position, all PKT_MAX_HDRS rows are.
+ *  - Why this layout: segment s is a batch of its own, {slab = dst + seg_start[s]*slot, slab_len = n_s*slot,
+ *    stride = slot, lens = out_len + seg_start[s], n = n_s} with the chain {n_hdrs + seg_start[s], hdr_type +
+ *    PKT_MAX_HDRS*seg_start[s], hdr_off + PKT_MAX_HDRS*seg_start[s]}: slot-major over ITS n_s packets, which a
+ *    slice of a [PKT_MAX_HDRS][m] column is not.  Every pkt_*_batch call takes it with no second parse.
+ *  - PKT_ERR_INVALID_ARG before any launch: the batch and slab rules with their texts (with dst, for a batch of
+ *    n > 0), m >= 2^32, a bad slot, a misaligned dst, a dst_len below m * slot, out_len without dst, nseg > 257,
+ *    nseg > 0 with a NULL seg_start, a seg_start that is not 8-byte aligned, a NULL perm with m > 0, an out column without its source.  m == 0 succeeds
+ *    and launches nothing.  Asynchronous on `stream`; keeps no ctx state.
+ *  - On the device: a bytes kernel (a wave covers 64 positions and walks their 16-byte chunks together: aligned
+ *    16-byte stores, the tail chunk masked) and a column kernel (a lane owns a position, reads perm[k] once for
+ *    all columns and finds its segment in a copy of seg_start in LDS).
+ * pkt_reorder_host is the same operation on HOST pointers: no ctx, no device.
+ * Out of scope: more than 256 buckets or a full key sort; variable-length packed output (pkt_pcap_write on a
+ * segment gives the packed form); concurrent calls on one handle. */
+#define PKT_DISPATCH_MAX_BUCKETS 256
+#define PKT_DISPATCH_MAX_TABLE   4096
+#define PKT_DISPATCH_DROP        0xFFFFu
+#define PKT_REORDER_MAX_SEGS     257
+typedef struct pkt_dispatch pkt_dispatch_t;
+int pkt_dispatch_create(pkt_ctx_t *ctx, uint32_t nbuckets, const uint16_t *table, uint32_t table_len,
+                        uint64_t max_n, pkt_dispatch_t **d);
+int pkt_dispatch_destroy(pkt_dispatch_t *d);
+int pkt_dispatch_batch(pkt_dispatch_t *d, const uint32_t *key, const uint8_t *select, uint64_t n,
+                       uint16_t *bucket, uint32_t *perm, uint32_t *rank, uint64_t *start, void *stream);
+int pkt_dispatch_host(uint32_t nbuckets, const uint16_t *table, uint32_t table_len, const uint32_t *key,
+                      const uint8_t *select, uint64_t n, uint16_t *bucket, uint32_t *perm, uint32_t *rank,
+                      uint64_t *start);
+int pkt_reorder_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_out_t *cols, const uint32_t *perm,
+                      uint64_t m, const uint64_t *seg_start, uint32_t nseg, uint8_t *dst, uint64_t dst_len,
+                      uint32_t slot, uint32_t *out_len, const pkt_out_t *out_cols, void *stream);
+int pkt_reorder_host(const pkt_batch_t *batch, const pkt_out_t *cols, const uint32_t *perm, uint64_t m,
+                     const uint64_t *seg_start, uint32_t nseg, uint8_t *dst, uint64_t dst_len, uint32_t slot,
+                     uint32_t *out_len, const pkt_out_t *out_cols);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -7,6 +7,7 @@
 #include "pktgpu_batch.hpp"
 #include "pktgpu_flow.hpp"
 #include "pktgpu_match.hpp"
+#include "pktgpu_dispatch.hpp"
 
 namespace {
 
@@ -733,6 +734,89 @@ int pkt_match_host(const pkt_match_term_t* terms, uint32_t nterms, const pkt_mat
         if (matched) matched[i] = bits;
         if (hits) hits[bits ? first : nrules] += 1;
         if (bytes) bytes[bits ? first : nrules] += len;
+    }
+    return PKT_SUCCESS;
+}
+
+// ---- pkt_dispatch_batch / pkt_reorder_batch on host pointers (the CPU models of pktgpu_dispatch.hip): a counting
+// sort in index order, and the gather a position at a time.
+int pkt_dispatch_host(uint32_t nbuckets, const uint16_t* table, uint32_t table_len, const uint32_t* key,
+                      const uint8_t* select, uint64_t n, uint16_t* bucket, uint32_t* perm, uint32_t* rank,
+                      uint64_t* start) {
+    if (dispatch_create_error(nbuckets, table, table_len, 0, false)) return PKT_ERR_INVALID_ARG;
+    if (dispatch_call_error(key, n, 0xFFFFFFFFull, start)) return PKT_ERR_INVALID_ARG;
+    if (!bucket && !perm && !rank && !start) return PKT_SUCCESS;
+    const uint32_t mask = table ? table_len - 1 : 0;
+    uint64_t at[PKT_DISPATCH_MAX_BUCKETS + 2] = {};  // at[b + 1] = bucket b's count, then its next position
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t b = dispatch_bucket(key[i], !select || select[i], nbuckets, table, mask);
+        at[b + 1]++;
+        if (bucket) bucket[i] = (uint16_t)(b < nbuckets ? b : PKT_DISPATCH_DROP);
+    }
+    uint64_t sum = 0;
+    for (uint32_t b = 0; b <= nbuckets; b++) {  // at[b] = the packets before bucket b
+        const uint64_t c = at[b + 1];
+        at[b] = sum;
+        if (start) start[b] = sum;
+        sum += c;
+    }
+    if (start) start[nbuckets + 1] = n;
+    if (!perm && !rank) return PKT_SUCCESS;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t b = dispatch_bucket(key[i], !select || select[i], nbuckets, table, mask);
+        const uint64_t pos = at[b]++;
+        if (perm) perm[pos] = (uint32_t)i;
+        if (rank) rank[i] = (uint32_t)pos;
+    }
+    return PKT_SUCCESS;
+}
+
+int pkt_reorder_host(const pkt_batch_t* b, const pkt_out_t* cols, const uint32_t* perm, uint64_t m,
+                     const uint64_t* seg_start, uint32_t nseg, uint8_t* dst, uint64_t dst_len, uint32_t slot,
+                     uint32_t* out_len, const pkt_out_t* out_cols) {
+    if (reorder_error(b, cols, perm, m, seg_start, nseg, dst, dst_len, slot, out_len, out_cols, false))
+        return PKT_ERR_INVALID_ARG;
+    if (m == 0) return PKT_SUCCESS;
+    uint64_t seg[PKT_REORDER_MAX_SEGS + 1] = {};
+    for (uint32_t s = 0; s <= nseg && nseg; s++) seg[s] = seg_start[s] < m ? seg_start[s] : m;
+    const BatchSrc src = batch_src(b);
+    const uint8_t* nhc = static_cast<const uint8_t*>(reorder_col(cols, kReorderNHdrs));
+    for (uint64_t k = 0; k < m; k++) {
+        const ReorderSeg sg = reorder_seg(seg, nseg, (uint32_t)k, (uint32_t)m);
+        if (!sg.live) continue;
+        const uint64_t p = perm[k];
+        const bool empty = p >= b->n;
+        if (dst) {
+            uint32_t len = 0;
+            if (!empty) {
+                const uint64_t off = pkt_off(src, p);
+                len = pkt_len(src, p, off);
+                len = len < slot ? len : slot;
+                if (len) memcpy(dst + k * slot, b->slab + off, len);
+            }
+            const uint32_t up = (len + 15u) & ~15u;
+            if (up > len) memset(dst + k * slot + len, 0, up - len);
+            if (out_len) out_len[k] = len;
+        }
+        uint32_t rows = PKT_MAX_HDRS;
+        if (nhc && !empty) rows = nhc[p] < PKT_MAX_HDRS ? nhc[p] : PKT_MAX_HDRS;
+        for (int c = 0; c < kReorderCols; c++) {
+            const uint8_t* in = static_cast<const uint8_t*>(reorder_col(cols, c));
+            uint8_t* out = static_cast<uint8_t*>(reorder_col(out_cols, c));
+            if (!in || !out) continue;
+            const uint32_t sz = kReorderColSize[c];
+            if (c == kReorderHdrType || c == kReorderHdrOff) {
+                for (uint32_t j = 0; j < rows; j++) {
+                    uint8_t* o = out + ((uint64_t)PKT_MAX_HDRS * sg.s0 + (uint64_t)j * sg.ns + (k - sg.s0)) * sz;
+                    if (empty) memset(o, 0, sz);
+                    else memcpy(o, in + ((uint64_t)j * b->n + p) * sz, sz);
+                }
+            } else if (empty) {
+                memset(out + k * sz, 0, sz);
+            } else {
+                memcpy(out + k * sz, in + p * sz, sz);
+            }
+        }
     }
     return PKT_SUCCESS;
 }

@@ -25,7 +25,7 @@ from . import schema
 from .schema import (ABI_VERSION, DEPTH_LIMIT, ENTRIES, ENTRY_ID, GROUPS, HDR_ID, HDR_NAMES,  # noqa: F401
                      HDR_SIZES, MAX_HDRS, OK, STATUS_NAMES, TRUNCATED)
 
-__all__ = ["Parser", "FlowTable", "MatchProgram", "match", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
+__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
 
 
 def resolve_columns(columns):
@@ -733,6 +733,68 @@ class Parser:
                                             self._stream(stream)), "pkt_match_batch")
         return res
 
+    def dispatcher(self, nbuckets, table=None, max_n=1 << 20):
+        """pkt_dispatch_create: a stable partition of up to `max_n` packets into `nbuckets` (1..256) queues ->
+        Dispatcher.  table=None is DIRECT mode (bucket = key when key < nbuckets, else dropped: an action, a rule
+        id, a shard number); a table (host integers, a power-of-two length up to 4096, entries < nbuckets or
+        pktgpu.DISPATCH_DROP) is the RSS indirection table: bucket = table[key & (len - 1)]."""
+        return Dispatcher(self, nbuckets, table, max_n)
+
+    def reorder(self, perm, slab=None, stride=None, n=None, offsets=None, lens=None, columns=None, start=None,
+                nseg=None, slot=None, m=None, out=None, stream=None):
+        """pkt_reorder_batch: packets and columns gathered by `perm` (uint32 device tensor: Dispatcher.run's, or
+        any index list; an entry >= n is an empty position) -> {"slab": uint8 [m * slot] or None, "slot", "lens":
+        uint32 [m] (min(length, slot)), "m", "columns": {name: tensor}, "start", "nseg"}.  `slab` (with stride /
+        offsets / lens as Parser.parse takes them; None = columns only, then pass n) is the source batch; `slot`
+        (a multiple of 16; default: a fixed-stride source's stride, rounded up) the bytes each packet gets; `columns`
+        a dict of source columns (any of pkt_out_t's, e.g. a parse's result) to gather.  `start` (uint64 device
+        tensor, Dispatcher.run's) with nseg (default: its length - 2, the kept buckets) lays the slot columns
+        hdr_type / hdr_off out per segment, so that every segment is a batch of its own (pktgpu.segments), and
+        leaves positions at or past start[nseg] (the dropped tail) unwritten: the freshly allocated outputs
+        hold zeros there.  Without `start` the slot columns come out as [16][m].  `out`: a previous result to
+        write into.  Asynchronous on `stream`."""
+        torch = _torch()
+        assert perm.dtype == torch.uint32 and perm.is_cuda and perm.is_contiguous()
+        m = perm.numel() if m is None else int(m)
+        if slab is not None:
+            b = self._batch(slab, n, stride, offsets, lens)
+        else:
+            b = self._lib.PktBatch()
+            b.n = int(n)
+        if start is not None:
+            assert start.dtype == torch.uint64 and start.is_cuda and start.is_contiguous()
+            nseg = start.numel() - 2 if nseg is None else int(nseg)
+        else:
+            nseg = 0
+        cols = dict(columns or {})
+        if out is None:
+            out = {"slab": None, "slot": 0, "lens": None, "m": m, "columns": {}, "start": start, "nseg": nseg}
+            if slab is not None:
+                if slot is None:
+                    if not stride:
+                        raise ValueError("reorder: an indexed source needs a slot")
+                    slot = (max(16, int(stride)) + 15) // 16 * 16
+                out["slot"] = int(slot)
+                out["slab"] = torch.zeros(m * int(slot), dtype=torch.uint8, device=self.torch_device)
+                out["lens"] = torch.zeros(m, dtype=torch.uint32, device=self.torch_device)
+            for c, t in cols.items():
+                shp = schema.column_shape(c, m)
+                if shp[0] == schema.MAX_HDRS and len(shp) == 2 and nseg:
+                    shp = (schema.MAX_HDRS * m,)
+                out["columns"][c] = torch.zeros(shp, dtype=t.dtype, device=self.torch_device)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        ci, co = self._lib.PktOut(), self._lib.PktOut()
+        for c, t in cols.items():
+            assert t.is_cuda and t.is_contiguous() and t.dtype == _tdtype(schema.column_dtype(c)), c
+            setattr(ci, c, ptr(t))
+            setattr(co, c, ptr(out["columns"][c]))
+        dst = out["slab"] if slab is not None else None
+        self._check(self._L.pkt_reorder_batch(self._ctx, ctypes.byref(b), ctypes.byref(ci), ptr(perm), m, ptr(start),
+                                              nseg, ptr(dst), dst.numel() if dst is not None else 0, out["slot"],
+                                              ptr(out["lens"]) if dst is not None else None, ctypes.byref(co),
+                                              self._stream(stream)), "pkt_reorder_batch")
+        return out
+
     def pcap_index_device_timed(self, buf, offsets, lens, stream=None):
         """pkt_pcap_index_device_timed into the caller's device `offsets` / `lens` (cap = their
         length): (record count, [guess, scan, emit] kernel ms from HIP events between them)."""
@@ -1132,6 +1194,170 @@ def match(slab, chain, rules, default=0, stride=None, n=None, offsets=None, lens
     if rc != 0:
         raise ValueError(f"pkt_match_host failed ({rc})")
     return res
+
+
+DISPATCH_DROP = schema.DISPATCH_DROP
+_DISPATCH_OUT = (("bucket", np.uint16), ("perm", np.uint32), ("rank", np.uint32), ("start", np.uint64))
+
+
+def _dispatch_table(table):
+    """(uint16 array or None, its length) of an indirection table given as integers."""
+    if table is None:
+        return None, 0
+    t = np.asarray(table)
+    if t.size and (t.min() < 0 or t.max() > 0xFFFF):
+        raise ValueError("dispatch: a table entry outside 0..0xFFFF")
+    return np.ascontiguousarray(t, np.uint16).reshape(-1), int(t.size)
+
+
+class Dispatcher:
+    """pkt_dispatch_t: a stable bucket partition on a parser's device (Parser.dispatcher).  One run at a time:
+    the runs share the handle's scratch."""
+
+    def __init__(self, parser, nbuckets, table=None, max_n=1 << 20):
+        self.parser = parser
+        self._L = parser._L
+        self.nbuckets, self.max_n = int(nbuckets), int(max_n)
+        tab, tlen = _dispatch_table(table)
+        h = ctypes.c_void_p()
+        parser._check(self._L.pkt_dispatch_create(parser._ctx, self.nbuckets, tab.ctypes.data if tab is not None else
+                                                  None, tlen, self.max_n, ctypes.byref(h)), "pkt_dispatch_create")
+        self._d = h
+
+    def run(self, key, select=None, outputs=("bucket", "perm", "rank", "start"), n=None, stream=None):
+        """pkt_dispatch_batch over `key` (uint32 device tensor [n]: flow_keys' "rss", match's "action", ...) and
+        an optional `select` (uint8 / bool device tensor: 0 drops the packet) -> a dict of the `outputs` asked
+        for among "bucket" (uint16: the packet's bucket, pktgpu.DISPATCH_DROP = dropped), "perm" (uint32:
+        perm[pos] = source index, buckets in order, source order within a bucket, the dropped last), "rank"
+        (uint32: its inverse) and "start" (uint64 [nbuckets + 2]: bucket b is positions [start[b], start[b + 1]),
+        start[nbuckets] the kept count).  Asynchronous on `stream`."""
+        torch = _torch()
+        p = self.parser
+        assert key.dtype == torch.uint32 and key.is_cuda and key.is_contiguous()
+        n = key.numel() if n is None else int(n)
+        if select is not None:
+            if select.dtype == torch.bool:
+                select = select.view(torch.uint8)
+            assert select.dtype == torch.uint8 and select.is_cuda and select.numel() >= n
+        res = {}
+        for name, dt in _DISPATCH_OUT:
+            if name in outputs:
+                res[name] = torch.empty(self.nbuckets + 2 if name == "start" else n, dtype=_tdtype(dt),
+                                        device=p.torch_device)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        p._check(self._L.pkt_dispatch_batch(self._d, ptr(key), ptr(select), n, *[ptr(res.get(k)) for k, _ in
+                                            _DISPATCH_OUT], p._stream(stream)), "pkt_dispatch_batch")
+        return res
+
+    def close(self):
+        if getattr(self, "_d", None):
+            self._L.pkt_dispatch_destroy(self._d)
+            self._d = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def dispatch(key, nbuckets, table=None, select=None, outputs=("bucket", "perm", "rank", "start"), n=None):
+    """pkt_dispatch_host over numpy arrays (no device): Dispatcher.run's arguments with the definition in place of
+    a handle -> the same dict of numpy arrays."""
+    from . import _lib
+    L = _lib.load()
+    key = np.ascontiguousarray(key, np.uint32).reshape(-1)
+    n = key.size if n is None else int(n)
+    tab, tlen = _dispatch_table(table)
+    if select is not None:
+        select = np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+    res = {name: np.zeros(int(nbuckets) + 2 if name == "start" else n, dt) for name, dt in _DISPATCH_OUT
+           if name in outputs}
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    rc = L.pkt_dispatch_host(int(nbuckets), tab.ctypes.data if tab is not None else None, tlen, ptr(key), ptr(select), n,
+                             *[ptr(res.get(k)) for k, _ in _DISPATCH_OUT])
+    if rc != 0:
+        raise ValueError(f"pkt_dispatch_host failed ({rc})")
+    return res
+
+
+def reorder(perm, slab=None, stride=None, n=None, offsets=None, lens=None, columns=None, start=None, nseg=None,
+            slot=None, m=None):
+    """pkt_reorder_host over numpy arrays (no device): Parser.reorder's arguments with numpy arrays -> the same
+    dict of numpy arrays."""
+    from . import _lib
+    L = _lib.load()
+    perm = np.ascontiguousarray(perm, np.uint32).reshape(-1)
+    m = perm.size if m is None else int(m)
+    keep = None
+    if slab is not None:
+        b, keep = _host_batch(_lib, dict(slab=slab, stride=stride, n=n, offsets=offsets, lens=lens))
+    else:
+        b = _lib.PktBatch()
+        b.n = int(n)
+    if start is not None:
+        start = np.ascontiguousarray(start, np.uint64).reshape(-1)
+        nseg = start.size - 2 if nseg is None else int(nseg)
+    else:
+        nseg = 0
+    out = {"slab": None, "slot": 0, "lens": None, "m": m, "columns": {}, "start": start, "nseg": nseg}
+    if slab is not None:
+        if slot is None:
+            if not stride:
+                raise ValueError("reorder: an indexed source needs a slot")
+            slot = (max(16, int(stride)) + 15) // 16 * 16
+        out["slot"] = int(slot)
+        out["slab"] = _aligned_zeros(m * int(slot))
+        out["lens"] = np.zeros(m, np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    ci, co, held = _lib.PktOut(), _lib.PktOut(), []
+    for c, a in (columns or {}).items():
+        a = np.ascontiguousarray(a, schema.column_dtype(c))
+        shp = schema.column_shape(c, m)
+        if shp[0] == schema.MAX_HDRS and len(shp) == 2 and nseg:
+            shp = (schema.MAX_HDRS * m,)
+        out["columns"][c] = np.zeros(shp, a.dtype)
+        held.append(a)
+        setattr(ci, c, ptr(a))
+        setattr(co, c, ptr(out["columns"][c]))
+    dst = out["slab"]
+    rc = L.pkt_reorder_host(ctypes.byref(b), ctypes.byref(ci), ptr(perm), m, ptr(start), nseg, ptr(dst),
+                            dst.size if dst is not None else 0, out["slot"], ptr(out["lens"]), ctypes.byref(co))
+    if rc != 0:
+        raise ValueError(f"pkt_reorder_host failed ({rc})")
+    return out
+
+
+def _aligned_zeros(nbytes, align=16):
+    """A zeroed uint8 array of nbytes whose first byte is `align`-byte aligned."""
+    raw = np.zeros(nbytes + align, np.uint8)
+    o = (-raw.ctypes.data) % align
+    return raw[o:o + nbytes]
+
+
+def segments(start, reordered):
+    """The per-bucket batches of a segmented Parser.reorder (or pktgpu.reorder) result: one small copy of
+    `start` to the host, then for each of the nseg buckets a dict {"slab", "stride", "n", "lens", "chain"}, views
+    into the reordered tensors.  slab / stride / n / lens are the keyword arguments Parser.pcap_write takes, and
+    with "chain" (the bucket's n_hdrs, hdr_type [16][n], hdr_off [16][n]; None when they were not gathered) the
+    ones Parser.match, flow_keys and l4_checksum take: `p.match(prog=prog, **seg)`."""
+    st = start.cpu().numpy() if hasattr(start, "cpu") else np.asarray(start)
+    m, slot, nseg = reordered["m"], reordered["slot"], reordered["nseg"]
+    cols = reordered["columns"]
+    out = []
+    for s in range(nseg):
+        s0, s1 = min(int(st[s]), m), min(int(st[s + 1]), m)
+        ns = max(0, s1 - s0)
+        seg = {"slab": reordered["slab"][s0 * slot:(s0 + ns) * slot] if reordered["slab"] is not None else None,
+               "stride": slot, "n": ns,
+               "lens": reordered["lens"][s0:s0 + ns] if reordered["lens"] is not None else None, "chain": None}
+        if all(c in cols for c in ("n_hdrs", "hdr_type", "hdr_off")):
+            seg["chain"] = {"n_hdrs": cols["n_hdrs"][s0:s0 + ns]}
+            for c in ("hdr_type", "hdr_off"):
+                seg["chain"][c] = cols[c].reshape(-1)[schema.MAX_HDRS * s0:schema.MAX_HDRS * (s0 + ns)].reshape(
+                    schema.MAX_HDRS, ns)
+        out.append(seg)
+    return out
 
 
 class FlowTable:

@@ -205,6 +205,18 @@ SIGNATURES = {
     "pkt_match_host": (ctypes.c_int, [ctypes.POINTER(PktMatchTerm), ctypes.c_uint32, ctypes.POINTER(PktMatchRule),
                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(PktBatch),
                                       ctypes.POINTER(PktChain), _P, _P, _P, _P, _P, _P]),
+    "pkt_dispatch_create": (ctypes.c_int, [_P, ctypes.c_uint32, _P, ctypes.c_uint32, ctypes.c_uint64,
+                                           ctypes.POINTER(_P)]),
+    "pkt_dispatch_destroy": (ctypes.c_int, [_P]),
+    "pkt_dispatch_batch": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _P, _P, _P, _P, _P]),
+    "pkt_dispatch_host": (ctypes.c_int, [ctypes.c_uint32, _P, ctypes.c_uint32, _P, _P, ctypes.c_uint64, _P, _P, _P,
+                                         _P]),
+    "pkt_reorder_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktOut), _P, ctypes.c_uint64,
+                                         _P, ctypes.c_uint32, _P, ctypes.c_uint64, ctypes.c_uint32, _P,
+                                         ctypes.POINTER(PktOut), _P]),
+    "pkt_reorder_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktOut), _P, ctypes.c_uint64, _P,
+                                        ctypes.c_uint32, _P, ctypes.c_uint64, ctypes.c_uint32, _P,
+                                        ctypes.POINTER(PktOut)]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),

@@ -36,6 +36,11 @@ MATCH_NOT = 1      # term flag: invert the term
 MATCH_HAS, MATCH_EQ, MATCH_RANGE, MATCH_LEN = range(4)
 MATCH_OPS = ["HAS", "EQ", "RANGE", "LEN"]
 
+# pkt_dispatch_* / pkt_reorder_batch (per-queue batches)
+DISPATCH_MAX_BUCKETS, DISPATCH_MAX_TABLE = 256, 4096
+DISPATCH_DROP = 0xFFFF  # bucket[i] of a packet no queue takes; a table entry that drops
+REORDER_MAX_SEGS = 257
+
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
                            ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])
