@@ -29,6 +29,10 @@ inline void check(int rc, const pkt_ctx_t* ctx, const char* what) {
         throw std::runtime_error(std::string(what) + " failed (" + std::to_string(rc) + "): " +
                                  (ctx ? pkt_ctx_last_error(ctx) : ""));
 }
+inline void lpm_check(int rc, const pkt_lpm_t* t, const char* what) {
+    if (rc != PKT_SUCCESS)
+        throw std::runtime_error(std::string(what) + " failed (" + std::to_string(rc) + "): " + pkt_lpm_last_error(t));
+}
 inline void hip_check(hipError_t e, const char* what) {
     if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
@@ -330,6 +334,31 @@ class Parser {
             *chain = pkt_chain_t{out_cols->n_hdrs + s0, out_cols->hdr_type + PKT_MAX_HDRS * s0,
                                  out_cols->hdr_off + PKT_MAX_HDRS * s0};
         return pkt_batch_t{dst + s0 * slot, (s1 - s0) * slot, nullptr, out_len + s0, slot, 0, s1 - s0};
+    }
+
+    // A longest-prefix-match route table compiled onto this context's device (pkt_lpm_create; max_bytes 0 = 1 GiB).
+    // The caller destroys it with pkt_lpm_destroy after the calls queued on it.
+    pkt_lpm_t* lpm(const std::vector<pkt_lpm_route_t>& routes, uint32_t default_nexthop = 0, uint64_t max_bytes = 0) {
+        pkt_lpm_t* t = nullptr;
+        check(pkt_lpm_create(ctx_, routes.empty() ? nullptr : routes.data(), (uint32_t)routes.size(), default_nexthop,
+                             max_bytes, &t), ctx_, "pkt_lpm_create");
+        return t;
+    }
+
+    // The longest matching route of every packet's destination (flags PKT_LPM_SRC: source) address
+    // (pkt_lpm_lookup_batch): route[i] its index (PKT_LPM_NONE: none), nexthop[i], plen[i], status[i]; each may be
+    // NULL.  Several lookups on one table may be in flight on different streams.  Asynchronous on `s`.
+    static void lpm_lookup(pkt_lpm_t* t, const pkt_batch_t& b, const pkt_chain_t& chain, uint32_t* nexthop,
+                           uint32_t* route = nullptr, uint8_t* plen = nullptr, uint8_t* status = nullptr,
+                           uint32_t which_ip = 0, uint32_t flags = 0, hipStream_t s = nullptr) {
+        lpm_check(pkt_lpm_lookup_batch(t, &b, &chain, which_ip, flags, route, nexthop, plen, status, s), t, "pkt_lpm_lookup_batch");
+    }
+
+    // The same over pkt_flow_key_batch's keys and status (pkt_lpm_lookup_keys).
+    static void lpm_lookup_keys(pkt_lpm_t* t, const pkt_flow_key_t* keys, const uint8_t* key_status, uint64_t n,
+                                uint32_t* nexthop, uint32_t* route = nullptr, uint8_t* plen = nullptr,
+                                uint8_t* status = nullptr, uint32_t flags = 0, hipStream_t s = nullptr) {
+        lpm_check(pkt_lpm_lookup_keys(t, keys, key_status, n, flags, route, nexthop, plen, status, s), t, "pkt_lpm_lookup_keys");
     }
 
    private:

@@ -1014,6 +1014,109 @@ int pkt_reorder_host(const pkt_batch_t *batch, const pkt_out_t *cols, const uint
                      const uint64_t *seg_start, uint32_t nseg, uint8_t *dst, uint64_t dst_len, uint32_t slot,
                      uint32_t *out_len, const pkt_out_t *out_cols);
 
+/* ---- longest-prefix-match route tables over a parsed batch ----
+ * Where an IP packet goes: the step between "classified" and "dispatched", and the natural producer of the 32-bit
+ * key pkt_dispatch_batch takes in DIRECT mode (a next hop, an egress port, a queue).  A route table of up to
+ * PKT_LPM_MAX_ROUTES IPv4 and IPv6 prefixes is compiled once into a device-resident multibit trie
+ * (pkt_lpm_create); one kernel then gives, per packet, the longest matching route and its next hop.  The
+ * reference defines nothing here, so this header fixes the semantics.
+ *
+ * pkt_lpm_create / pkt_lpm_create_host
+ *  - Blocking, and the only allocation (the pkt_match_create pattern).  `routes` is HOST memory, captured at the
+ *    call.  max_bytes bounds the compiled table; 0 means 1 GiB.  nroutes == 0 is legal: every IP packet is
+ *    PKT_LPM_NO_ROUTE.
+ *  - PKT_ERR_INVALID_ARG with a text starting "pkt_lpm": nroutes > PKT_LPM_MAX_ROUTES; NULL routes with nroutes >
+ *    0; an ipver that is neither 4 nor 6; a plen above 32 (IPv4) or 128 (IPv6); a non-zero `zero`; any address bit
+ *    at or past plen set (IPv4's bytes 4..15 included); two routes with the same (ipver, plen, prefix).
+ *    PKT_ERR_UNSUPPORTED when the compiled table needs more than max_bytes; the text names the bytes needed.
+ *    The text of a failed pkt_lpm_create is in pkt_ctx_last_error; that of a failed pkt_lpm_create_host, which has
+ *    neither ctx nor handle, in pkt_lpm_last_error(NULL) of the calling thread.
+ *  - The table: one root of 2^16 entries per IP version (the address's first 16 bits), below it nodes of 256
+ *    entries (8 bits each): at most 3 levels for IPv4 and 15 for IPv6.  An entry is a uint32_t: bit 31 set = the
+ *    low bits are a child node's index, otherwise a route's index + 1, 0 = no route.  A route of length L <= 16
+ *    fills 2^(16-L) root entries, one with 16+8k < L <= 24+8k fills 2^(24+8k-L) entries of one node of level k+1;
+ *    routes go in by ascending plen, so a longer prefix overwrites a shorter one where they overlap, and a new
+ *    child node starts as a copy of the entry it hangs under (leaf pushing).  A lookup is a chain of dependent
+ *    4-byte loads that ends at the first entry without bit 31, with no backtracking; a route's {nexthop, plen}
+ *    record (8 bytes) is read once at the end.  pkt_lpm_info: routes_v4 / routes_v6, nodes_v4 / nodes_v6 (256-entry
+ *    nodes, roots not counted), depth_v4 / depth_v6 (the deepest level a route reached, the root being 1; 0 for no
+ *    route), bytes = both roots (2 x 256 KiB) + 1 KiB per node + 8 per route.
+ *
+ * The result for one address: the route of the address's IP version with the greatest plen whose first plen bits
+ * equal the address's (unique: duplicates are refused); a /0 route matches every address of its version.  On a
+ * match status = PKT_LPM_OK, route[i] = the route's index in the caller's array, nexthop[i] = its nexthop, plen[i]
+ * = its plen.  For every other status route = PKT_LPM_NONE, nexthop = default_nexthop, plen = 0xFF.
+ *
+ * pkt_lpm_lookup_batch
+ *  - batch / chain / which_ip (PKT_FLOW_LAST included) and the min(n_hdrs, PKT_MAX_HDRS) rule are exactly
+ *    pkt_flow_key_batch's; whatever the columns hold, no byte outside the packet is used.  The address is bytes
+ *    16..19 (destination) or, with PKT_LPM_SRC, 12..15 of an IPv4 entry, and 24..39 or 8..23 of an IPv6 entry.
+ *    No such entry: PKT_LPM_NO_IP.  The entry's 20 / 40 bytes not inside the packet: PKT_LPM_SPAN (the test
+ *    PKT_FLOW_SPAN makes for the IP header).
+ *  - PKT_ERR_INVALID_ARG before any launch, with a text in pkt_lpm_last_error: pkt_flow_key_batch's refusals (the
+ *    batch and slab rules, a NULL chain or, with n > 0, chain column, n >= 2^32, a bad which_ip) and unknown flag
+ *    bits.
+ * pkt_lpm_lookup_keys
+ *  - The address is keys[i].dst (or .src with PKT_LPM_SRC) and the version keys[i].ipver: pkt_flow_key_batch's
+ *    output.  A packet is PKT_LPM_SKIPPED if key_status is non-NULL and key_status[i] != 0, or if ipver is neither
+ *    4 nor 6.  With PKT_FLOW_SYMMETRIC keys the two ends may have been swapped: which one is the destination is
+ *    then the caller's concern.
+ *  - PKT_ERR_INVALID_ARG: NULL keys with n > 0, keys not 2-byte aligned, n >= 2^32, unknown flag bits.
+ * Both lookups
+ *  - route / nexthop: uint32_t[n]; plen / status: uint8_t[n].  Every output may be NULL; with all four NULL nothing
+ *    is launched.  n == 0 succeeds and launches nothing.
+ *  - Asynchronous on `stream`.  A lookup never writes the table, so several lookups on one handle may be in flight
+ *    on different streams.  pkt_lpm_destroy is the caller's to order after the queued calls.
+ *  - A handle from pkt_lpm_create_host takes HOST pointers everywhere, ignores `stream`, runs a sequential loop
+ *    and touches no device (the pkt_flow_table_create_host pattern; the slab's alignment rule is waived).  Both
+ *    kinds of handle share one compile and one walk.
+ *  - On the device a lane owns a packet: one kernel, no lane waits for another, no atomics.  The loop over levels
+ *    is bounded by the table's depth, not by 3 / 15.
+ * Out of scope: incremental insert and delete (rebuild, then swap handles); per-route hit counters (a bincount of
+ * `route`); path compression of long IPv6 chains; ECMP / multipath; IPv4 options and IPv6 extension headers (the
+ * walk models neither). */
+typedef struct pkt_lpm_route {     /* 24 bytes */
+    uint8_t  addr[16];             /* wire bytes; IPv4 in [0..4), the rest 0 */
+    uint8_t  ipver;                /* 4 or 6 */
+    uint8_t  plen;                 /* 0..32 / 0..128 */
+    uint16_t zero;
+    uint32_t nexthop;              /* caller-defined: a port, a queue, an adjacency index */
+} pkt_lpm_route_t;
+typedef struct pkt_lpm_info {      /* 56 bytes */
+    uint64_t routes_v4;
+    uint64_t routes_v6;
+    uint64_t nodes_v4;
+    uint64_t nodes_v6;
+    uint64_t depth_v4;
+    uint64_t depth_v6;
+    uint64_t bytes;
+} pkt_lpm_info_t;
+typedef enum pkt_lpm_status {
+    PKT_LPM_OK       = 0,
+    PKT_LPM_NO_ROUTE = 1, /* no route of the address's version covers it */
+    PKT_LPM_NO_IP    = 2, /* the chain has no such IPv4 / IPv6 entry */
+    PKT_LPM_SPAN     = 3, /* the IP header does not lie inside the packet */
+    PKT_LPM_SKIPPED  = 4  /* lookup_keys: key_status[i] != 0, or an ipver that is neither 4 nor 6 */
+} pkt_lpm_status_t;
+#define PKT_LPM_NONE       0xFFFFFFFFu /* route[i] when status != PKT_LPM_OK */
+#define PKT_LPM_SRC        1u          /* flags: look up the source address (default: destination) */
+#define PKT_LPM_MAX_ROUTES (1u << 24)
+typedef struct pkt_lpm pkt_lpm_t;
+size_t pkt_sizeof_lpm_route(void);
+int pkt_lpm_create(pkt_ctx_t *ctx, const pkt_lpm_route_t *routes, uint32_t nroutes, uint32_t default_nexthop,
+                   uint64_t max_bytes, pkt_lpm_t **lpm);
+int pkt_lpm_create_host(const pkt_lpm_route_t *routes, uint32_t nroutes, uint32_t default_nexthop,
+                        uint64_t max_bytes, pkt_lpm_t **lpm);
+int pkt_lpm_info(const pkt_lpm_t *lpm, pkt_lpm_info_t *info);
+int pkt_lpm_lookup_batch(pkt_lpm_t *lpm, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                         uint32_t flags, uint32_t *route, uint32_t *nexthop, uint8_t *plen, uint8_t *status,
+                         void *stream);
+int pkt_lpm_lookup_keys(pkt_lpm_t *lpm, const pkt_flow_key_t *keys, const uint8_t *key_status, uint64_t n,
+                        uint32_t flags, uint32_t *route, uint32_t *nexthop, uint8_t *plen, uint8_t *status,
+                        void *stream);
+int pkt_lpm_destroy(pkt_lpm_t *lpm);
+const char *pkt_lpm_last_error(const pkt_lpm_t *lpm);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -8,6 +8,7 @@
 #include "pktgpu_flow.hpp"
 #include "pktgpu_match.hpp"
 #include "pktgpu_dispatch.hpp"
+#include "pktgpu_lpm.hpp"
 
 namespace {
 
@@ -820,6 +821,135 @@ int pkt_reorder_host(const pkt_batch_t* b, const pkt_out_t* cols, const uint32_t
     }
     return PKT_SUCCESS;
 }
+
+// ---- pkt_lpm_*: the public calls, and the host handle's sequential loops (the device handle: pktgpu_lpm.hip).
+// The compile and the walk are pktgpu_lpm.hpp's, shared with the kernel.
+size_t pkt_sizeof_lpm_route(void) { return sizeof(pkt_lpm_route_t); }
+
+static thread_local std::string t_lpm_create_err;  // pkt_lpm_last_error(NULL): the thread's last failed create_host
+
+int pkt_lpm_create_host(const pkt_lpm_route_t* routes, uint32_t nroutes, uint32_t default_nexthop, uint64_t max_bytes,
+                        pkt_lpm_t** out) {
+    if (!out) {
+        t_lpm_create_err = "pkt_lpm_create_host: null argument";
+        return PKT_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    LpmImage img;
+    const int rc = lpm_compile(routes, nroutes, max_bytes, img, t_lpm_create_err);
+    if (rc != PKT_SUCCESS) return rc;
+    pkt_lpm* t = new pkt_lpm;
+    t->info = img.info;
+    t->host_words.swap(img.words);
+    t->view = img.view(t->host_words.data(), default_nexthop);
+    *out = t;
+    return PKT_SUCCESS;
+}
+
+int pkt_lpm_info(const pkt_lpm_t* t, pkt_lpm_info_t* info) {
+    if (!t || !info) return PKT_ERR_INVALID_ARG;
+    *info = t->info;
+    return PKT_SUCCESS;
+}
+
+static void lpm_store(const LpmCall& c, uint64_t i, const LpmResult& r) {
+    if (c.route) c.route[i] = r.route;
+    if (c.nexthop) c.nexthop[i] = r.nexthop;
+    if (c.plen) c.plen[i] = (uint8_t)r.plen;
+    if (c.status) c.status[i] = (uint8_t)r.status;
+}
+
+static uint32_t rd_be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+
+int pkt_lpm_lookup_batch(pkt_lpm_t* t, const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
+                         uint32_t* route, uint32_t* nexthop, uint8_t* plen, uint8_t* status, void* stream) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (!b || !chain) return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_batch: null argument");
+    if (b->n >= (1ull << 32)) return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_batch: n >= 2^32");
+    if (flags & ~PKT_LPM_SRC) return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_batch: unknown flag bits");
+    if (which_ip >= PKT_MAX_HDRS && which_ip != PKT_FLOW_LAST)
+        return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_batch: which_ip is neither below 16 nor PKT_FLOW_LAST");
+    const uint64_t n = b->n;
+    if (n == 0) return PKT_SUCCESS;
+    if (!chain->n_hdrs || !chain->hdr_type || !chain->hdr_off)
+        return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_batch: null chain column");
+    const char* msg = t->ops ? batch_slab16_error(b) : batch_null_slab(b) ? "null slab" : nullptr;
+    if (!msg) msg = batch_index_error(b);
+    if (msg) {
+        t->err = std::string("pkt_lpm_lookup_batch: ") + msg;
+        return PKT_ERR_INVALID_ARG;
+    }
+    if (!route && !nexthop && !plen && !status) return PKT_SUCCESS;
+    const LpmCall c{false,   batch_src(b), n,     chain->n_hdrs, chain->hdr_type, chain->hdr_off, nullptr, nullptr,
+                    which_ip, flags,       route, nexthop,       plen,            status};
+    if (t->ops) return t->ops->lookup(t, c, stream);
+    const bool need_rec = nexthop || plen;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t off = pkt_off(c.src, i);
+        const uint32_t len = pkt_len(c.src, i, off);
+        uint32_t nh = chain->n_hdrs[i], seen = 0, slot = PKT_MAX_HDRS;
+        nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+        for (uint32_t j = 0; j < nh; j++) {
+            const uint8_t ty = chain->hdr_type[j * n + i];
+            if (ty != PKT_HDR_IPV4 && ty != PKT_HDR_IPV6) continue;
+            if (which_ip == PKT_FLOW_LAST || seen == which_ip) slot = j;
+            seen++;
+        }
+        LpmResult r = lpm_miss(t->view, PKT_LPM_NO_IP);
+        if (slot < PKT_MAX_HDRS) {
+            const bool v4 = chain->hdr_type[slot * n + i] == PKT_HDR_IPV4;
+            const uint32_t ip = chain->hdr_off[slot * n + i];
+            if (ip + (v4 ? 20u : 40u) > len) {
+                r.status = PKT_LPM_SPAN;
+            } else {
+                const bool src = flags & PKT_LPM_SRC;
+                const uint8_t* a = b->slab + off + ip + (v4 ? (src ? 12u : 16u) : (src ? 8u : 24u));
+                uint32_t w[4] = {rd_be32(a), 0, 0, 0};
+                for (uint32_t q = 1; q < 4 && !v4; q++) w[q] = rd_be32(a + 4 * q);
+                r = lpm_lookup(w, v4, t->view, need_rec);
+            }
+        }
+        lpm_store(c, i, r);
+    }
+    return PKT_SUCCESS;
+}
+
+int pkt_lpm_lookup_keys(pkt_lpm_t* t, const pkt_flow_key_t* keys, const uint8_t* key_status, uint64_t n, uint32_t flags,
+                        uint32_t* route, uint32_t* nexthop, uint8_t* plen, uint8_t* status, void* stream) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (n >= (1ull << 32)) return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_keys: n >= 2^32");
+    if (flags & ~PKT_LPM_SRC) return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_keys: unknown flag bits");
+    if ((uintptr_t)keys & 1) return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_keys: keys not 2-byte aligned");
+    if (n == 0) return PKT_SUCCESS;
+    if (!keys) return lpm_fail(t, PKT_ERR_INVALID_ARG, "pkt_lpm_lookup_keys: null keys");
+    if (!route && !nexthop && !plen && !status) return PKT_SUCCESS;
+    const LpmCall c{true,  BatchSrc{}, n,     nullptr, nullptr, nullptr, reinterpret_cast<const uint8_t*>(keys), key_status,
+                    0,     flags,      route, nexthop, plen,    status};
+    if (t->ops) return t->ops->lookup(t, c, stream);
+    const bool need_rec = nexthop || plen;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint8_t* k = c.keys + 40 * i;
+        const uint32_t ver = k[37];
+        LpmResult r = lpm_miss(t->view, PKT_LPM_SKIPPED);
+        if (!(key_status && key_status[i]) && (ver == 4 || ver == 6)) {
+            const uint8_t* a = k + (flags & PKT_LPM_SRC ? 0 : 16);
+            uint32_t w[4] = {rd_be32(a), 0, 0, 0};
+            for (uint32_t q = 1; q < 4 && ver == 6; q++) w[q] = rd_be32(a + 4 * q);
+            r = lpm_lookup(w, ver == 4, t->view, need_rec);
+        }
+        lpm_store(c, i, r);
+    }
+    return PKT_SUCCESS;
+}
+
+int pkt_lpm_destroy(pkt_lpm_t* t) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    const int rc = t->ops ? t->ops->destroy(t) : PKT_SUCCESS;
+    delete t;
+    return rc;
+}
+
+const char* pkt_lpm_last_error(const pkt_lpm_t* t) { return t ? t->err.c_str() : t_lpm_create_err.c_str(); }
 
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,
 // packet.rs:724-731: insert / set_payload).

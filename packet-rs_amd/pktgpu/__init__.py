@@ -25,7 +25,7 @@ from . import schema
 from .schema import (ABI_VERSION, DEPTH_LIMIT, ENTRIES, ENTRY_ID, GROUPS, HDR_ID, HDR_NAMES,  # noqa: F401
                      HDR_SIZES, MAX_HDRS, OK, STATUS_NAMES, TRUNCATED)
 
-__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
+__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
 
 
 def resolve_columns(columns):
@@ -739,6 +739,14 @@ class Parser:
         id, a shard number); a table (host integers, a power-of-two length up to 4096, entries < nbuckets or
         pktgpu.DISPATCH_DROP) is the RSS indirection table: bucket = table[key & (len - 1)]."""
         return Dispatcher(self, nbuckets, table, max_n)
+
+    def lpm(self, routes, default_nexthop=0, max_bytes=0, host=False):
+        """pkt_lpm_create: compile a route table into a multibit trie on this parser's device -> Lpm.  `routes`: an
+        iterable of ("10.0.0.0/8", nexthop) / ("2001:db8::/32", nexthop) pairs, or a numpy array of
+        schema.LPM_ROUTE_DTYPE (pkt_lpm_route_t).  `default_nexthop`: the next hop of a packet no route covers;
+        `max_bytes`: the most the compiled table may take (0 = 1 GiB).  host=True gives the host handle
+        (pkt_lpm_create_host: numpy arrays in and out, no device)."""
+        return Lpm(None if host else self, routes, default_nexthop, max_bytes)
 
     def reorder(self, perm, slab=None, stride=None, n=None, offsets=None, lens=None, columns=None, start=None,
                 nseg=None, slot=None, m=None, out=None, stream=None):
@@ -1476,6 +1484,152 @@ class FlowTable:
     def close(self):
         if getattr(self, "_t", None):
             self._L.pkt_flow_table_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+LPM_NONE = schema.LPM_NONE
+_LPM_OUT = (("route", np.uint32), ("nexthop", np.uint32), ("plen", np.uint8), ("status", np.uint8))
+
+
+def lpm_routes(routes):
+    """A route list as a C-contiguous array of schema.LPM_ROUTE_DTYPE (pkt_lpm_route_t): an iterable of
+    ("10.0.0.0/8", nexthop) / ("2001:db8::/32", nexthop) pairs (strings or stdlib ipaddress networks; host bits
+    must be zero), or such an array, which passes through."""
+    import ipaddress
+    if isinstance(routes, np.ndarray):
+        if routes.dtype != schema.LPM_ROUTE_DTYPE:
+            raise ValueError("lpm: a route array must have schema.LPM_ROUTE_DTYPE")
+        return np.ascontiguousarray(routes).reshape(-1)
+    routes = list(routes)
+    arr = np.zeros(len(routes), schema.LPM_ROUTE_DTYPE)
+    for i, (net, nh) in enumerate(routes):
+        net = ipaddress.ip_network(net) if isinstance(net, str) else net
+        raw = net.network_address.packed
+        arr["addr"][i, :len(raw)] = np.frombuffer(raw, np.uint8)
+        arr["ipver"][i] = net.version
+        arr["plen"][i] = net.prefixlen
+        arr["nexthop"][i] = int(nh)
+    return arr
+
+
+class Lpm:
+    """pkt_lpm_t: a compiled longest-prefix-match route table (Parser.lpm).  Lpm(parser, routes) lives on the parser's
+    device and takes and gives device tensors; Lpm(None, routes) is the host handle over numpy arrays (no device).
+
+        lpm = p.lpm([("10.0.0.0/8", 1), ("10.1.0.0/16", 2), ("2001:db8::/32", 3)], default_nexthop=255)
+        r = lpm.lookup(batch, chain)             # {"route", "nexthop", "plen", "status"}
+        d = p.dispatcher(4).run(r["nexthop"])    # next hops 0..3 are queues, the rest is dropped
+    """
+
+    def __init__(self, parser, routes, default_nexthop=0, max_bytes=0):
+        from . import _lib
+        self._lib = _lib
+        self._L = _lib.load()
+        self.parser = parser
+        self.routes = lpm_routes(routes)
+        self.default_nexthop = int(default_nexthop)
+        n = self.routes.size
+        rp = self.routes.ctypes.data if n else None
+        h = ctypes.c_void_p()
+        if parser is None:
+            rc = self._L.pkt_lpm_create_host(rp, n, self.default_nexthop, int(max_bytes), ctypes.byref(h))
+            if rc != 0:
+                msg = self._L.pkt_lpm_last_error(None)
+                raise ValueError(f"pkt_lpm_create_host failed ({rc}): {msg.decode() if msg else ''}")
+        else:
+            parser._check(self._L.pkt_lpm_create(parser._ctx, rp, n, self.default_nexthop, int(max_bytes),
+                                                 ctypes.byref(h)), "pkt_lpm_create")
+        self._t = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self._L.pkt_lpm_last_error(self._t)
+            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+    def _stream(self, stream):
+        return None if self.parser is None else self.parser._stream(stream)
+
+    def _outputs(self, n, outputs):
+        """The output arrays asked for (torch on the device handle's device, numpy for a host handle) and their
+        addresses in pkt_lpm_lookup_*'s order."""
+        bad = set(outputs) - {k for k, _ in _LPM_OUT}
+        if bad:
+            raise ValueError(f"lpm: unknown outputs {sorted(bad)}")
+        if self.parser is None:
+            res = {k: np.zeros(n, dt) for k, dt in _LPM_OUT if k in outputs}
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        else:
+            torch = _torch()
+            res = {k: torch.empty(n, dtype=_tdtype(dt), device=self.parser.torch_device) for k, dt in _LPM_OUT
+                   if k in outputs}
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        return res, [ptr(res.get(k)) for k, _ in _LPM_OUT]
+
+    def lookup(self, batch, chain, which_ip=0, src=False, outputs=("route", "nexthop", "plen", "status"), stream=None):
+        """pkt_lpm_lookup_batch: the longest matching route of every packet's destination (src=True: source)
+        address -> a dict of the `outputs` asked for among "route" (uint32: the route's index in the table given
+        to Parser.lpm, pktgpu.LPM_NONE = none), "nexthop" (uint32: the route's, else the default), "plen" (uint8:
+        the route's length, 0xFF = none) and "status" (uint8: schema.LPM_OK / _NO_ROUTE / _NO_IP / _SPAN).
+        `batch`: a dict with "slab" and "stride" / "n" / "offsets" / "lens" as Parser.parse takes them, or a
+        (slab, offsets, lens) tuple (PcapStream.batch()'s); `chain`: the chain columns of a parse of it.  `which_ip`: the k-th IPv4 / IPv6
+        header of the list, counted together from 0, or pktgpu.FLOW_LAST (the innermost).  Device tensors for a
+        device handle, numpy arrays for a host handle.  Asynchronous on `stream`."""
+        if isinstance(batch, (tuple, list)):
+            batch = dict(zip(("slab", "offsets", "lens"), batch))
+        g = lambda k: batch.get(k)  # noqa: E731
+        if self.parser is None:
+            b, keep = _host_batch(self._lib, batch)
+            cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                    np.ascontiguousarray(chain["hdr_off"], np.uint16))
+            ch = self._lib.PktChain(*[c.ctypes.data for c in cols])
+        else:
+            b = self.parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
+            ch = self.parser._chain(chain)
+        res, ptrs = self._outputs(b.n, outputs)
+        self._check(self._L.pkt_lpm_lookup_batch(self._t, ctypes.byref(b), ctypes.byref(ch), int(which_ip),
+                                                 schema.LPM_SRC if src else 0, *ptrs, self._stream(stream)),
+                    "pkt_lpm_lookup_batch")
+        return res
+
+    def lookup_keys(self, keys, status=None, src=False, outputs=("route", "nexthop", "plen", "status"), stream=None):
+        """pkt_lpm_lookup_keys: the same over flow keys (uint8 [n, 40]: flow_keys' "keys", or its whole dict, whose
+        "status" is then taken too): the address is the key's dst (src=True: src).  A packet whose `status` is not 0
+        or whose key has no IP version is schema.LPM_SKIPPED."""
+        if isinstance(keys, dict):
+            status = keys.get("status") if status is None else status
+            keys = keys["keys"]
+        n = int(keys.shape[0])
+        if self.parser is None:
+            keys = np.ascontiguousarray(keys, np.uint8)
+            status = None if status is None else np.ascontiguousarray(status, np.uint8)
+            kp = keys.ctypes.data if n else None
+            sp = status.ctypes.data if status is not None and n else None
+        else:
+            torch = _torch()
+            assert keys.is_cuda and keys.dtype == torch.uint8 and keys.is_contiguous()
+            assert status is None or (status.is_cuda and status.dtype == torch.uint8 and status.numel() >= n)
+            kp = keys.data_ptr() if n else None
+            sp = status.data_ptr() if status is not None and n else None
+        res, ptrs = self._outputs(n, outputs)
+        self._check(self._L.pkt_lpm_lookup_keys(self._t, kp, sp, n, schema.LPM_SRC if src else 0, *ptrs,
+                                                self._stream(stream)), "pkt_lpm_lookup_keys")
+        return res
+
+    def info(self):
+        """pkt_lpm_info -> {"routes_v4", "routes_v6", "nodes_v4", "nodes_v6", "depth_v4", "depth_v6", "bytes"}."""
+        i = self._lib.PktLpmInfo()
+        self._check(self._L.pkt_lpm_info(self._t, ctypes.byref(i)), "pkt_lpm_info")
+        return {k: int(getattr(i, k)) for k, _ in i._fields_}
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self._L.pkt_lpm_destroy(self._t)
             self._t = None
 
     def __del__(self):

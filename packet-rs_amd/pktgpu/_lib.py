@@ -78,6 +78,16 @@ class PktMatchRule(ctypes.Structure):
     _fields_ = [("first_term", ctypes.c_uint16), ("nterms", ctypes.c_uint16), ("action", ctypes.c_uint32)]
 
 
+class PktLpmRoute(ctypes.Structure):
+    _fields_ = [("addr", ctypes.c_uint8 * 16), ("ipver", ctypes.c_uint8), ("plen", ctypes.c_uint8),
+                ("zero", ctypes.c_uint16), ("nexthop", ctypes.c_uint32)]
+
+
+class PktLpmInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("routes_v4", "routes_v6", "nodes_v4", "nodes_v6", "depth_v4", "depth_v6",
+                                               "bytes")]
+
+
 # Every function declared in include/pktgpu.h: name -> (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -217,6 +227,15 @@ SIGNATURES = {
     "pkt_reorder_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktOut), _P, ctypes.c_uint64, _P,
                                         ctypes.c_uint32, _P, ctypes.c_uint64, ctypes.c_uint32, _P,
                                         ctypes.POINTER(PktOut)]),
+    "pkt_sizeof_lpm_route": (ctypes.c_size_t, []),
+    "pkt_lpm_create": (ctypes.c_int, [_P, _P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(_P)]),
+    "pkt_lpm_create_host": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(_P)]),
+    "pkt_lpm_info": (ctypes.c_int, [_P, ctypes.POINTER(PktLpmInfo)]),
+    "pkt_lpm_lookup_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                            ctypes.c_uint32, _P, _P, _P, _P, _P]),
+    "pkt_lpm_lookup_keys": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P, _P, _P]),
+    "pkt_lpm_destroy": (ctypes.c_int, [_P]),
+    "pkt_lpm_last_error": (ctypes.c_char_p, [_P]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -298,7 +317,8 @@ def load():
             or L.pkt_sizeof_flow_key() != ctypes.sizeof(PktFlowKey) \
             or L.pkt_sizeof_flow_record() != ctypes.sizeof(PktFlowRecord) \
             or L.pkt_sizeof_match_term() != ctypes.sizeof(PktMatchTerm) \
-            or L.pkt_sizeof_match_rule() != ctypes.sizeof(PktMatchRule):
+            or L.pkt_sizeof_match_rule() != ctypes.sizeof(PktMatchRule) \
+            or L.pkt_sizeof_lpm_route() != ctypes.sizeof(PktLpmRoute):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L
     return L

@@ -41,11 +41,22 @@ DISPATCH_MAX_BUCKETS, DISPATCH_MAX_TABLE = 256, 4096
 DISPATCH_DROP = 0xFFFF  # bucket[i] of a packet no queue takes; a table entry that drops
 REORDER_MAX_SEGS = 257
 
+# pkt_lpm_* (longest-prefix-match route tables)
+LPM_OK, LPM_NO_ROUTE, LPM_NO_IP, LPM_SPAN, LPM_SKIPPED = range(5)
+LPM_STATUS = ["OK", "NO_ROUTE", "NO_IP", "SPAN", "SKIPPED"]
+LPM_NONE = 0xFFFFFFFF  # route[i] when status != LPM_OK
+LPM_SRC = 1            # flags: look up the source address
+LPM_MAX_ROUTES = 1 << 24
+
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
                            ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])
 FLOW_RECORD_DTYPE = np.dtype([("key", FLOW_KEY_DTYPE), ("first", np.uint64), ("pkts", np.uint64, 2),
                               ("bytes", np.uint64, 2)])
+
+# pkt_lpm_route_t as a numpy record
+LPM_ROUTE_DTYPE = np.dtype([("addr", np.uint8, 16), ("ipver", np.uint8), ("plen", np.uint8), ("zero", np.uint16),
+                            ("nexthop", np.uint32)])
 
 # pkt_hdr_type_t -> Header::name() of the reference (headers.rs:529-827)
 HDR_NAMES = [
