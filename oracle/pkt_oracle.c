@@ -645,7 +645,8 @@ int orc_extract_fields(const pkt_batch_t *b, const pkt_chain_t *chain, const pkt
         packet_bounds(b, i, &p, &len);
         for (uint32_t s = 0; s < nspec; s++) {
             int occ = 0, hit = -1;
-            for (int j = 0; j < chain->n_hdrs[i]; j++) {
+            /* the slot rows are [PKT_MAX_HDRS][n]: a larger n_hdrs names no further slots */
+            for (int j = 0; j < chain->n_hdrs[i] && j < PKT_MAX_HDRS; j++) {
                 if (chain->hdr_type[(uint64_t)j * b->n + i] == specs[s].hdr_type) {
                     if (occ == specs[s].occurrence) { hit = j; break; }
                     occ++;
@@ -767,7 +768,7 @@ void orc_set_bit_range(uint8_t *map, size_t msb, size_t lsb, uint64_t value) {
 
 static int find_hdr(const pkt_chain_t *c, uint64_t n, uint64_t i, int type, int occurrence) {
     int occ = 0;
-    for (int j = 0; j < c->n_hdrs[i]; j++)
+    for (int j = 0; j < c->n_hdrs[i] && j < PKT_MAX_HDRS; j++) /* (the slot rows are [PKT_MAX_HDRS][n]) */
         if (c->hdr_type[(uint64_t)j * n + i] == type) {
             if (occ == occurrence) return j;
             occ++;
