@@ -361,6 +361,26 @@ class Parser {
         lpm_check(pkt_lpm_lookup_keys(t, keys, key_status, n, flags, route, nexthop, plen, status, s), t, "pkt_lpm_lookup_keys");
     }
 
+    // An adjacency table on this context's device (pkt_fwd_create).  The caller destroys it with pkt_fwd_destroy
+    // after the calls queued on it.
+    pkt_fwd_t* forwarder(const std::vector<pkt_fwd_adj_t>& adj) {
+        pkt_fwd_t* f = nullptr;
+        check(pkt_fwd_create(ctx_, adj.empty() ? nullptr : adj.data(), (uint32_t)adj.size(), &f), ctx_, "pkt_fwd_create");
+        return f;
+    }
+
+    // The L3 forwarding rewrite of a routed batch, in place (pkt_fwd_batch): the adjacency index of packet i is
+    // nexthop[i], or, with `lpm` (and nexthop NULL), its destination's route in that table; port[i] is the
+    // adjacency's port for a forwarded packet and PKT_FWD_NONE otherwise, which pkt_dispatch_batch in DIRECT mode
+    // drops.  status / port / adj_index / hits / bytes may each be NULL.  Asynchronous on `s`.
+    void forward(pkt_fwd_t* f, const pkt_batch_t& b, const pkt_chain_t& chain, const uint32_t* nexthop, uint32_t* port,
+                 uint8_t* status = nullptr, uint32_t* adj_index = nullptr, pkt_lpm_t* lpm = nullptr,
+                 const uint8_t* select = nullptr, uint32_t which_ip = 0, uint32_t flags = 0, uint64_t* hits = nullptr,
+                 uint64_t* bytes = nullptr, hipStream_t s = nullptr) {
+        check(pkt_fwd_batch(f, &b, &chain, which_ip, flags, lpm, nexthop, select, status, port, adj_index, hits, bytes, s),
+              ctx_, "pkt_fwd_batch");
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

@@ -1117,6 +1117,110 @@ int pkt_lpm_lookup_keys(pkt_lpm_t *lpm, const pkt_flow_key_t *keys, const uint8_
 int pkt_lpm_destroy(pkt_lpm_t *lpm);
 const char *pkt_lpm_last_error(const pkt_lpm_t *lpm);
 
+/* ---- L3 forwarding rewrite over a routed batch ----
+ * The step a router takes between "routed" and "queued": resolve the next hop's adjacency, rewrite the two MAC
+ * addresses, decrement the TTL / hop limit and refuse the packets whose TTL has run out, fix the IPv4 header
+ * checksum, check the egress MTU and say which port the packet leaves on.  pkt_lpm's next hop is "a port, a queue, an
+ * adjacency index"; this call resolves the adjacency index, in one kernel, optionally fused with the route lookup.
+ * The reference defines nothing here, so this header fixes the semantics.
+ *
+ * pkt_fwd_create: blocking, and the only allocation (the pkt_match_create pattern).  `adj` is HOST memory, captured at
+ * the call; nadj == 0 is legal (every packet that gets as far as the adjacency is PKT_FWD_NO_ADJ).
+ * PKT_ERR_INVALID_ARG with a text starting "pkt_fwd" in pkt_ctx_last_error: nadj > PKT_FWD_MAX_ADJ; NULL adj with
+ * nadj > 0; an `action` above 2; a non-zero `zero`.  The device copy is padded (32 bytes an entry, so that an entry
+ * is two aligned 16-byte loads); that layout is private.
+ *
+ * pkt_fwd_batch, per packet i: the first test that applies gives status[i], and a packet whose status is not
+ * PKT_FWD_OK is not written at all.
+ *  1. select != NULL && select[i] == 0: PKT_FWD_SKIPPED.
+ *  2. The IP entry is found exactly as in pkt_flow_key_batch / pkt_lpm_lookup_batch: which_ip (PKT_FLOW_LAST
+ *     included) counts the IPv4 and IPv6 entries of the list together, over min(n_hdrs, PKT_MAX_HDRS) entries; a
+ *     which_ip in 16..0xFE is refused.  No such entry: PKT_FWD_NO_IP.  Its 20 / 40 bytes not inside the packet's
+ *     length (under the pkt_batch_t clamp rules): PKT_FWD_SPAN.
+ *  3. Unless PKT_FWD_KEEP_L2: the Ether entry is the list entry of type PKT_HDR_ETHER with the greatest index below
+ *     the IP entry's index (for a VXLAN packet's inner IP that is the inner Ethernet header).  None:
+ *     PKT_FWD_NO_ETHER.  Its 14 bytes not inside the packet: PKT_FWD_SPAN.
+ *  4. t = byte 8 of an IPv4 entry (ttl), byte 7 of an IPv6 entry (hop limit).  t <= 1: PKT_FWD_TTL.
+ *  5. The adjacency index a: nexthop[i] when `nexthop` is given; otherwise what pkt_lpm_lookup_batch(lpm, batch,
+ *     chain, which_ip, 0, ...) writes to nexthop[i]: the next hop of the destination address's route, or the
+ *     table's default_nexthop when no route covers it.  Exactly one of lpm / nexthop must be non-NULL.
+ *     a >= nadj: PKT_FWD_NO_ADJ.  adj[a].action PKT_FWD_ACT_DROP: PKT_FWD_DROP; PKT_FWD_ACT_PUNT: PKT_FWD_PUNT.
+ *  6. adj[a].mtu != 0 and the L3 length > mtu: PKT_FWD_MTU.  The L3 length is bytes 2..3 of an IPv4 entry, or 40 +
+ *     bytes 4..5 of an IPv6 entry, big-endian: it comes from the IP header, not from the packet's length.
+ *  7. PKT_FWD_OK.
+ * The writes of an OK packet (none with PKT_FWD_NO_WRITE):
+ *  - Ether bytes 0..5 = dmac and 6..11 = smac (not with PKT_FWD_KEEP_L2).
+ *  - IPv4 byte 8 = t - 1; IPv6 byte 7 = t - 1.
+ *  - IPv4 bytes 10..11 = HC', big-endian, by RFC 1624 eq. 3: with HC the stored checksum, m = bytes 8..9 as a
+ *    big-endian word and m' = m - 0x0100: s = (~HC & 0xFFFF) + (~m & 0xFFFF) + m', folded twice (s = (s & 0xFFFF)
+ *    + (s >> 16)), HC' = ~s & 0xFFFF.  This is deliberately NOT Packet::ipv4_checksum: the header is not summed
+ *    again and there is no Q1 fold, so a checksum that was wrong before stays wrong by the same amount, as it does
+ *    in a forwarding plane (pkt_set_fields_csum / pkt_ipv4_update_checksum are the recomputing calls).
+ *  - Stores may rewrite other bytes of the packet's own Ether bytes 0..11 and of its own IP header with their
+ *    unchanged values; no byte outside those two ranges is written, not even with its own value.  Packets of one
+ *    batch must not overlap (the pkt_set_fields rule).  Columns that are not a parse of the batch give
+ *    unspecified packet bytes, but never an access outside the packet.
+ * Outputs: device arrays of n elements, each may be NULL.  status: uint8_t.  port: uint32_t, adj[a].port iff
+ * status is PKT_FWD_OK, else PKT_FWD_NONE: pkt_dispatch_batch in DIRECT mode then drops what was not forwarded.
+ * adj_index: uint32_t, a for every packet that reached step 5, else PKT_FWD_NONE.  hits / bytes: device
+ * uint64_t[PKT_FWD_STATUS_COUNT], 8-byte aligned, caller-owned, ADDED to as pkt_match_batch's counters are:
+ * hits[status] += 1, bytes[status] += the packet's length under the batch clamp; integer atomics, exact: every call
+ * adds exactly n to sum(hits).  With every output NULL and PKT_FWD_NO_WRITE set nothing is launched.
+ *  - PKT_ERR_INVALID_ARG before any launch (the text, starting "pkt_fwd", in pkt_ctx_last_error of the ctx the
+ *    handle was created on): pkt_flow_key_batch's batch and slab rules, a NULL chain or, with n > 0, chain column,
+ *    n >= 2^32, a bad which_ip, unknown flag bits, both or neither of lpm / nexthop, an lpm that is a host handle
+ *    or was created on another device, hits / bytes that are not 8-byte aligned.  n == 0 succeeds, launches
+ *    nothing and leaves the counters alone.
+ *  - Asynchronous on `stream`.  The call never writes the handle or the lpm table, so calls over different batches
+ *    may be in flight on different streams.  pkt_fwd_destroy is the caller's to order after the queued calls.
+ *  - On the device a lane owns a packet: one kernel, the IP header's first 12 bytes (and, with lpm, the address)
+ *    by the aligned 16-byte chunks that hold them, the adjacency by two 16-byte loads, narrow stores to the bytes
+ *    named above; a block merges its per-status counts in LDS and adds once per non-zero (status, counter).  No
+ *    lane waits for another.
+ * pkt_fwd_host is the same operation on HOST pointers: no ctx, no device, no handle.  Its lpm, if given, must be a
+ * handle from pkt_lpm_create_host; the slab's 16-byte alignment rule is waived, as for that handle.
+ * Out of scope: VLAN push or rewrite (pkt_edit_batch / pkt_set_fields); ICMP time-exceeded and fragmentation-needed
+ * generation, and fragmentation itself; ECMP; per-adjacency counters (a bincount of adj_index); NAT; IPv4 options and
+ * IPv6 extension headers (the walk models neither). */
+typedef struct pkt_fwd_adj {       /* 20 bytes */
+    uint8_t  dmac[6];              /* written to the Ether header's bytes 0..5 */
+    uint8_t  smac[6];              /* written to bytes 6..11 */
+    uint32_t port;                 /* caller-defined egress port / queue: the key pkt_dispatch_batch takes (DIRECT) */
+    uint16_t mtu;                  /* 0 = no check; else the largest L3 length forwarded */
+    uint8_t  action;               /* pkt_fwd_action_t */
+    uint8_t  zero;
+} pkt_fwd_adj_t;
+typedef enum pkt_fwd_action { PKT_FWD_ACT_FORWARD = 0, PKT_FWD_ACT_DROP = 1, PKT_FWD_ACT_PUNT = 2 } pkt_fwd_action_t;
+typedef enum pkt_fwd_status {
+    PKT_FWD_OK       = 0,
+    PKT_FWD_SKIPPED  = 1, /* select[i] == 0 */
+    PKT_FWD_NO_IP    = 2, /* the chain has no such IPv4 / IPv6 entry */
+    PKT_FWD_SPAN     = 3, /* the IP or the Ether header does not lie inside the packet */
+    PKT_FWD_NO_ETHER = 4, /* no Ether entry before the IP entry */
+    PKT_FWD_TTL      = 5, /* ttl / hop limit <= 1 */
+    PKT_FWD_NO_ADJ   = 6, /* the adjacency index is not below nadj */
+    PKT_FWD_DROP     = 7, /* the adjacency's action */
+    PKT_FWD_PUNT     = 8, /* the adjacency's action */
+    PKT_FWD_MTU      = 9  /* the L3 length is above the adjacency's mtu */
+} pkt_fwd_status_t;
+#define PKT_FWD_STATUS_COUNT 10
+#define PKT_FWD_NONE     0xFFFFFFFFu   /* port[i] / adj_index[i] when there is none */
+#define PKT_FWD_KEEP_L2  1u            /* flags: no Ether entry is looked for, no MAC is written */
+#define PKT_FWD_NO_WRITE 2u            /* flags: decide everything, store nothing into the slab */
+#define PKT_FWD_MAX_ADJ  (1u << 20)
+typedef struct pkt_fwd pkt_fwd_t;
+size_t pkt_sizeof_fwd_adj(void);
+int pkt_fwd_create(pkt_ctx_t *ctx, const pkt_fwd_adj_t *adj, uint32_t nadj, pkt_fwd_t **f);
+int pkt_fwd_destroy(pkt_fwd_t *f);
+int pkt_fwd_batch(pkt_fwd_t *f, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                  uint32_t flags, pkt_lpm_t *lpm, const uint32_t *nexthop, const uint8_t *select,
+                  uint8_t *status, uint32_t *port, uint32_t *adj_index, uint64_t *hits, uint64_t *bytes,
+                  void *stream);
+int pkt_fwd_host(const pkt_fwd_adj_t *adj, uint32_t nadj, const pkt_batch_t *batch, const pkt_chain_t *chain,
+                 uint32_t which_ip, uint32_t flags, pkt_lpm_t *lpm, const uint32_t *nexthop,
+                 const uint8_t *select, uint8_t *status, uint32_t *port, uint32_t *adj_index,
+                 uint64_t *hits, uint64_t *bytes);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -9,6 +9,7 @@
 #include "pktgpu_match.hpp"
 #include "pktgpu_dispatch.hpp"
 #include "pktgpu_lpm.hpp"
+#include "pktgpu_fwd.hpp"
 
 namespace {
 
@@ -950,6 +951,87 @@ int pkt_lpm_destroy(pkt_lpm_t* t) {
 }
 
 const char* pkt_lpm_last_error(const pkt_lpm_t* t) { return t ? t->err.c_str() : t_lpm_create_err.c_str(); }
+
+// ---- pkt_fwd_batch on host pointers (the CPU twin of pktgpu_fwd.hip): a sequential loop over the packets with the
+// decision, the checksum arithmetic and the refusals of pktgpu_fwd.hpp, which the kernel shares; the packet's bytes
+// are read and written a byte at a time.
+size_t pkt_sizeof_fwd_adj(void) { return sizeof(pkt_fwd_adj_t); }
+
+int pkt_fwd_host(const pkt_fwd_adj_t* adj, uint32_t nadj, const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip,
+                 uint32_t flags, pkt_lpm_t* lpm, const uint32_t* nexthop, const uint8_t* select, uint8_t* status,
+                 uint32_t* port, uint32_t* adj_index, uint64_t* hits, uint64_t* bytes) {
+    if (fwd_adj_error(adj, nadj)) return PKT_ERR_INVALID_ARG;
+    if (fwd_call_error(b, chain, which_ip, flags, lpm, nexthop, hits, bytes, false, 0)) return PKT_ERR_INVALID_ARG;
+    const uint64_t n = b->n;
+    if (n == 0) return PKT_SUCCESS;
+    if (fwd_batch_error(b, chain, false)) return PKT_ERR_INVALID_ARG;
+    const bool keep_l2 = flags & PKT_FWD_KEEP_L2, write = !(flags & PKT_FWD_NO_WRITE);
+    if (!status && !port && !adj_index && !hits && !bytes && !write) return PKT_SUCCESS;
+    const BatchSrc src = batch_src(b);
+    uint8_t* slab = const_cast<uint8_t*>(b->slab);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t off = pkt_off(src, i);
+        const uint32_t len = pkt_len(src, i, off);
+        uint32_t st = PKT_FWD_SKIPPED, out_port = PKT_FWD_NONE, out_adj = PKT_FWD_NONE;
+        if (!select || select[i]) {
+            uint32_t nh = chain->n_hdrs[i];
+            nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+            FwdFind f;
+            for (uint32_t j = 0; j < nh; j++) fwd_find_step(f, which_ip, chain->hdr_type[j * n + i], chain->hdr_off[j * n + i]);
+            st = fwd_find_status(f, len, keep_l2);
+            if (st == PKT_FWD_OK) {
+                const bool v4 = f.ipt == PKT_HDR_IPV4;
+                uint8_t* ip = slab + off + f.ipo;
+                uint32_t h[3];
+                for (uint32_t k = 0; k < 3; k++) h[k] = ip[4 * k] | (uint32_t)ip[4 * k + 1] << 8 | (uint32_t)ip[4 * k + 2] << 16 | (uint32_t)ip[4 * k + 3] << 24;
+                const FwdIp fi = fwd_ip_fields(h, v4);
+                if (fi.t <= 1u) {
+                    st = PKT_FWD_TTL;
+                } else {
+                    uint32_t a;
+                    if (lpm) {
+                        const uint8_t* d = ip + (v4 ? 16 : 24);
+                        uint32_t w[4] = {rd_be32(d), 0, 0, 0};
+                        for (uint32_t q = 1; q < 4 && !v4; q++) w[q] = rd_be32(d + 4 * q);
+                        a = lpm_lookup(w, v4, lpm->view, true).nexthop;
+                    } else {
+                        a = nexthop[i];
+                    }
+                    out_adj = a;
+                    if (a >= nadj) {
+                        st = PKT_FWD_NO_ADJ;
+                    } else {
+                        const FwdAdj e = fwd_pack(adj[a]);
+                        st = fwd_adj_status(e.w[4], fi.l3len);
+                        if (st == PKT_FWD_OK) {
+                            out_port = e.w[3];
+                            if (write) {
+                                if (!keep_l2) {
+                                    memcpy(slab + off + f.eth, adj[a].dmac, 6);
+                                    memcpy(slab + off + f.eth + 6, adj[a].smac, 6);
+                                }
+                                if (v4) {
+                                    const uint32_t nw = fwd_v4_word(h[2]);
+                                    ip[8] = (uint8_t)nw;
+                                    ip[10] = (uint8_t)(nw >> 16);
+                                    ip[11] = (uint8_t)(nw >> 24);
+                                } else {
+                                    ip[7] = (uint8_t)(fi.t - 1u);
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        if (status) status[i] = (uint8_t)st;
+        if (port) port[i] = out_port;
+        if (adj_index) adj_index[i] = out_adj;
+        if (hits) hits[st] += 1;
+        if (bytes) bytes[st] += len;
+    }
+    return PKT_SUCCESS;
+}
 
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,
 // packet.rs:724-731: insert / set_payload).

@@ -25,7 +25,7 @@ from . import schema
 from .schema import (ABI_VERSION, DEPTH_LIMIT, ENTRIES, ENTRY_ID, GROUPS, HDR_ID, HDR_NAMES,  # noqa: F401
                      HDR_SIZES, MAX_HDRS, OK, STATUS_NAMES, TRUNCATED)
 
-__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
+__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "Forwarder", "fwd_adjacencies", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
 
 
 def resolve_columns(columns):
@@ -747,6 +747,13 @@ class Parser:
         `max_bytes`: the most the compiled table may take (0 = 1 GiB).  host=True gives the host handle
         (pkt_lpm_create_host: numpy arrays in and out, no device)."""
         return Lpm(None if host else self, routes, default_nexthop, max_bytes)
+
+    def forwarder(self, adj, host=False):
+        """pkt_fwd_create: an adjacency table on this parser's device -> Forwarder.  `adj`: an iterable of (dmac, smac,
+        port[, mtu[, action]]) with the MACs as "aa:bb:cc:dd:ee:ff" strings or 6-byte objects, mtu 0 = no check and
+        action one of schema.FWD_ACT_FORWARD / _DROP / _PUNT, or a numpy array of schema.FWD_ADJ_DTYPE
+        (pkt_fwd_adj_t).  host=True gives the host form (pkt_fwd_host: numpy arrays in and out, no device)."""
+        return Forwarder(None if host else self, adj)
 
     def reorder(self, perm, slab=None, stride=None, n=None, offsets=None, lens=None, columns=None, start=None,
                 nseg=None, slot=None, m=None, out=None, stream=None):
@@ -1631,6 +1638,140 @@ class Lpm:
         if getattr(self, "_t", None):
             self._L.pkt_lpm_destroy(self._t)
             self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+(FWD_OK, FWD_SKIPPED, FWD_NO_IP, FWD_SPAN, FWD_NO_ETHER, FWD_TTL, FWD_NO_ADJ, FWD_DROP, FWD_PUNT, FWD_MTU) = range(10)
+FWD_ACT_FORWARD, FWD_ACT_DROP, FWD_ACT_PUNT = schema.FWD_ACT_FORWARD, schema.FWD_ACT_DROP, schema.FWD_ACT_PUNT
+FWD_NONE, FWD_KEEP_L2, FWD_NO_WRITE = schema.FWD_NONE, schema.FWD_KEEP_L2, schema.FWD_NO_WRITE
+_FWD_OUT = (("status", np.uint8), ("port", np.uint32), ("adj_index", np.uint32))
+
+
+def _mac(m):
+    raw = bytes(int(x, 16) for x in m.split(":")) if isinstance(m, str) else bytes(m)
+    if len(raw) != 6:
+        raise ValueError(f"forwarder: a MAC address has 6 bytes, not {m!r}")
+    return np.frombuffer(raw, np.uint8)
+
+
+def fwd_adjacencies(adj):
+    """An adjacency list as a C-contiguous array of schema.FWD_ADJ_DTYPE (pkt_fwd_adj_t): an iterable of (dmac,
+    smac, port[, mtu[, action]]) tuples, or such an array, which passes through."""
+    if isinstance(adj, np.ndarray):
+        if adj.dtype != schema.FWD_ADJ_DTYPE:
+            raise ValueError("forwarder: an adjacency array must have schema.FWD_ADJ_DTYPE")
+        return np.ascontiguousarray(adj).reshape(-1)
+    adj = list(adj)
+    arr = np.zeros(len(adj), schema.FWD_ADJ_DTYPE)
+    for i, (dmac, smac, port, *rest) in enumerate(adj):
+        arr["dmac"][i], arr["smac"][i], arr["port"][i] = _mac(dmac), _mac(smac), int(port)
+        arr["mtu"][i] = int(rest[0]) if rest else 0
+        arr["action"][i] = int(rest[1]) if len(rest) > 1 else schema.FWD_ACT_FORWARD
+    return arr
+
+
+class Forwarder:
+    """pkt_fwd_t: an adjacency table and the L3 forwarding rewrite over a routed batch (Parser.forwarder).
+    Forwarder(parser, adj) lives on the parser's device and takes and gives device tensors; Forwarder(None, adj) is
+    the host form over numpy arrays (pkt_fwd_host, no device).
+
+        fwd = p.forwarder([("02:00:00:00:00:01", "02:00:00:00:00:fe", 0), ("02:00:00:00:00:02", "02:00:00:00:00:fe", 1, 1500)])
+        r = fwd.run(batch, chain, lpm=lpm)         # {"status", "port", "adj_index"}; the OK packets are rewritten in place
+        d = p.dispatcher(4).run(r["port"])         # what was not forwarded has port FWD_NONE and is dropped
+    """
+
+    def __init__(self, parser, adj):
+        from . import _lib
+        self._lib = _lib
+        self._L = _lib.load()
+        self.parser = parser
+        self.adj = fwd_adjacencies(adj)
+        self._f = None
+        if parser is not None:
+            h = ctypes.c_void_p()
+            n = self.adj.size
+            parser._check(self._L.pkt_fwd_create(parser._ctx, self.adj.ctypes.data if n else None, n, ctypes.byref(h)),
+                          "pkt_fwd_create")
+            self._f = h
+
+    def run(self, batch, chain, nexthop=None, lpm=None, which_ip=0, keep_l2=False, write=True, select=None,
+            outputs=("status", "port", "adj_index"), hits=None, bytes=None, stream=None):
+        """pkt_fwd_batch: per packet, find the IP entry (`which_ip` as Lpm.lookup takes it) and the Ether entry before
+        it, take the adjacency index from `nexthop` (uint32 [n]) or from `lpm` (an Lpm: the destination's route, fused
+        into the same kernel) and, for a packet that may be forwarded, write the adjacency's MACs, decrement the ttl /
+        hop limit and update the IPv4 checksum incrementally, IN PLACE in the batch's slab -> a dict of the `outputs`
+        asked for among "status" (uint8: pktgpu.FWD_OK / _SKIPPED / _NO_IP / _SPAN / _NO_ETHER / _TTL / _NO_ADJ /
+        _DROP / _PUNT / _MTU), "port" (uint32: the adjacency's port for an OK packet, else pktgpu.FWD_NONE) and
+        "adj_index" (uint32).  keep_l2: no Ether entry is looked for and no MAC written; write=False: decide only.
+        `select` (uint8 [n]): a packet whose byte is 0 is skipped.  hits / bytes: True allocates zeroed uint64 [10]
+        per-status counters and returns them; an array passed in is accumulated into.  `batch` / `chain`: the forms
+        Lpm.lookup takes.  Device tensors for a device handle, numpy arrays for the host form.  Asynchronous on
+        `stream`."""
+        bad = set(outputs) - {k for k, _ in _FWD_OUT}
+        if bad:
+            raise ValueError(f"forwarder: unknown outputs {sorted(bad)}")
+        if isinstance(batch, (tuple, list)):
+            batch = dict(zip(("slab", "offsets", "lens"), batch))
+        g = lambda k: batch.get(k)  # noqa: E731
+        host = self.parser is None
+        if lpm is not None and (lpm.parser is None) != host:
+            raise ValueError("forwarder: a device handle takes a device Lpm, the host form a host Lpm")
+        flags = (schema.FWD_KEEP_L2 if keep_l2 else 0) | (0 if write else schema.FWD_NO_WRITE)
+        nc = schema.FWD_STATUS_COUNT
+        if host:
+            slab = batch["slab"]
+            if write and not (isinstance(slab, np.ndarray) and slab.dtype == np.uint8 and slab.flags.c_contiguous
+                              and slab.flags.writeable):
+                raise ValueError("forwarder: the host form rewrites batch['slab'] in place: a writeable C-contiguous uint8 array")
+            b, keep = _host_batch(self._lib, batch)
+            cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                    np.ascontiguousarray(chain["hdr_off"], np.uint16))
+            ch = self._lib.PktChain(*[c.ctypes.data for c in cols])
+            nexthop = None if nexthop is None else np.ascontiguousarray(nexthop, np.uint32)
+            select = None if select is None else np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+            res = {k: np.zeros(b.n, dt) for k, dt in _FWD_OUT if k in outputs}
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+            zeros = lambda: np.zeros(nc, np.uint64)  # noqa: E731
+            ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
+        else:
+            torch = _torch()
+            b = self.parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
+            ch = self.parser._chain(chain)
+            assert nexthop is None or (nexthop.is_cuda and nexthop.dtype == torch.uint32 and nexthop.is_contiguous()
+                                       and nexthop.numel() >= b.n)
+            assert select is None or (select.is_cuda and select.dtype == torch.uint8 and select.is_contiguous()
+                                      and select.numel() >= b.n)
+            dev = self.parser.torch_device
+            res = {k: torch.empty(b.n, dtype=_tdtype(dt), device=dev) for k, dt in _FWD_OUT if k in outputs}
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+            zeros = lambda: torch.zeros(nc, dtype=torch.uint64, device=dev)  # noqa: E731
+            ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
+        for name, c in (("hits", hits), ("bytes", bytes)):
+            if c is True:
+                c = zeros()
+            if c is not None and c is not False:
+                assert ok(c), f"forwarder: {name} is a contiguous uint64 [{nc}] array"
+                res[name] = c
+        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), flags, None if lpm is None else lpm._t, ptr(nexthop),
+                ptr(select), *[ptr(res.get(k)) for k, _ in _FWD_OUT], ptr(res.get("hits")), ptr(res.get("bytes")))
+        if host:
+            n = self.adj.size
+            rc = self._L.pkt_fwd_host(self.adj.ctypes.data if n else None, n, *args)
+            if rc != 0:
+                raise ValueError(f"pkt_fwd_host failed ({rc})")
+        else:
+            self.parser._check(self._L.pkt_fwd_batch(self._f, *args, self.parser._stream(stream)), "pkt_fwd_batch")
+        return res
+
+    def close(self):
+        if getattr(self, "_f", None):
+            self._L.pkt_fwd_destroy(self._f)
+            self._f = None
 
     def __del__(self):
         try:

@@ -88,6 +88,11 @@ class PktLpmInfo(ctypes.Structure):
                                                "bytes")]
 
 
+class PktFwdAdj(ctypes.Structure):
+    _fields_ = [("dmac", ctypes.c_uint8 * 6), ("smac", ctypes.c_uint8 * 6), ("port", ctypes.c_uint32),
+                ("mtu", ctypes.c_uint16), ("action", ctypes.c_uint8), ("zero", ctypes.c_uint8)]
+
+
 # Every function declared in include/pktgpu.h: name -> (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -236,6 +241,13 @@ SIGNATURES = {
     "pkt_lpm_lookup_keys": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P, _P, _P]),
     "pkt_lpm_destroy": (ctypes.c_int, [_P]),
     "pkt_lpm_last_error": (ctypes.c_char_p, [_P]),
+    "pkt_sizeof_fwd_adj": (ctypes.c_size_t, []),
+    "pkt_fwd_create": (ctypes.c_int, [_P, _P, ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "pkt_fwd_destroy": (ctypes.c_int, [_P]),
+    "pkt_fwd_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                     ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pkt_fwd_host": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain),
+                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -318,7 +330,8 @@ def load():
             or L.pkt_sizeof_flow_record() != ctypes.sizeof(PktFlowRecord) \
             or L.pkt_sizeof_match_term() != ctypes.sizeof(PktMatchTerm) \
             or L.pkt_sizeof_match_rule() != ctypes.sizeof(PktMatchRule) \
-            or L.pkt_sizeof_lpm_route() != ctypes.sizeof(PktLpmRoute):
+            or L.pkt_sizeof_lpm_route() != ctypes.sizeof(PktLpmRoute) \
+            or L.pkt_sizeof_fwd_adj() != ctypes.sizeof(PktFwdAdj):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L
     return L

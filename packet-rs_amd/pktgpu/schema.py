@@ -48,6 +48,17 @@ LPM_NONE = 0xFFFFFFFF  # route[i] when status != LPM_OK
 LPM_SRC = 1            # flags: look up the source address
 LPM_MAX_ROUTES = 1 << 24
 
+# pkt_fwd_* (L3 forwarding rewrite)
+(FWD_OK, FWD_SKIPPED, FWD_NO_IP, FWD_SPAN, FWD_NO_ETHER, FWD_TTL, FWD_NO_ADJ, FWD_DROP, FWD_PUNT,
+ FWD_MTU) = range(10)
+FWD_STATUS = ["OK", "SKIPPED", "NO_IP", "SPAN", "NO_ETHER", "TTL", "NO_ADJ", "DROP", "PUNT", "MTU"]
+FWD_STATUS_COUNT = 10
+FWD_ACT_FORWARD, FWD_ACT_DROP, FWD_ACT_PUNT = range(3)
+FWD_NONE = 0xFFFFFFFF  # port[i] / adj_index[i] when there is none
+FWD_KEEP_L2 = 1        # flags: no Ether entry is looked for, no MAC is written
+FWD_NO_WRITE = 2       # flags: decide everything, store nothing into the slab
+FWD_MAX_ADJ = 1 << 20
+
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
                            ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])
@@ -57,6 +68,10 @@ FLOW_RECORD_DTYPE = np.dtype([("key", FLOW_KEY_DTYPE), ("first", np.uint64), ("p
 # pkt_lpm_route_t as a numpy record
 LPM_ROUTE_DTYPE = np.dtype([("addr", np.uint8, 16), ("ipver", np.uint8), ("plen", np.uint8), ("zero", np.uint16),
                             ("nexthop", np.uint32)])
+
+# pkt_fwd_adj_t as a numpy record
+FWD_ADJ_DTYPE = np.dtype([("dmac", np.uint8, 6), ("smac", np.uint8, 6), ("port", np.uint32), ("mtu", np.uint16),
+                          ("action", np.uint8), ("zero", np.uint8)])
 
 # pkt_hdr_type_t -> Header::name() of the reference (headers.rs:529-827)
 HDR_NAMES = [
