@@ -381,6 +381,36 @@ class Parser {
               ctx_, "pkt_fwd_batch");
     }
 
+    // What Parser::fragment reports: the outputs and their rounded bytes (the capacities to retry with when `fits`
+    // is false: the outputs did not fit out_cap / dst_len, and dst and the per-output arrays are unspecified).
+    struct FragTotals {
+        uint64_t n_out = 0, bytes = 0;
+        bool fits = true;
+    };
+
+    // IPv4 fragmentation of a batch to a per-packet MTU (pkt_frag_batch): every packet whose L3 length is above its
+    // mtu (mtu[i], or mtu_all when `mtu` is NULL; 0 = no limit) becomes fragments, every other packet that may pass
+    // goes through whole, packed at 16-byte-aligned offsets of dst; out_off / out_len (out_cap entries, empty past
+    // n_out) make dst an indexed batch and out_chain its chain columns (strided by out_cap).  With
+    // PKT_FRAG_NO_WRITE in `flags` only status / nfrag / first / hits and the totals are produced: the sizing pass.
+    // Waits for the totals.
+    FragTotals fragment(const pkt_batch_t& b, const pkt_chain_t& chain, const uint16_t* mtu, uint32_t mtu_all, uint8_t* dst,
+                        uint64_t dst_len, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len,
+                        const pkt_chain_t* out_chain = nullptr, uint32_t* src_index = nullptr, uint16_t* frag_index = nullptr,
+                        uint8_t* status = nullptr, uint32_t* nfrag = nullptr, uint32_t* first = nullptr,
+                        const uint8_t* select = nullptr, uint32_t which_ip = 0, uint32_t flags = 0, uint64_t* hits = nullptr,
+                        hipStream_t s = nullptr) {
+        FragTotals t;
+        const int rc = pkt_frag_batch(ctx_, &b, &chain, which_ip, flags, mtu, mtu_all, select, status, nfrag, first, dst, dst_len,
+                                      out_cap, out_off, out_len, src_index, frag_index, out_chain, hits, &t.bytes, &t.n_out, s);
+        if (rc == PKT_ERR_INVALID_ARG && (t.n_out || t.bytes)) {
+            t.fits = false;
+            return t;
+        }
+        check(rc, ctx_, "pkt_frag_batch");
+        return t;
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

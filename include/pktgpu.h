@@ -1180,7 +1180,7 @@ const char *pkt_lpm_last_error(const pkt_lpm_t *lpm);
  * pkt_fwd_host is the same operation on HOST pointers: no ctx, no device, no handle.  Its lpm, if given, must be a
  * handle from pkt_lpm_create_host; the slab's 16-byte alignment rule is waived, as for that handle.
  * Out of scope: VLAN push or rewrite (pkt_edit_batch / pkt_set_fields); ICMP time-exceeded and fragmentation-needed
- * generation, and fragmentation itself; ECMP; per-adjacency counters (a bincount of adj_index); NAT; IPv4 options and
+ * generation (fragmentation itself is pkt_frag_batch, below: it takes the PKT_FWD_MTU packets); ECMP; per-adjacency counters (a bincount of adj_index); NAT; IPv4 options and
  * IPv6 extension headers (the walk models neither). */
 typedef struct pkt_fwd_adj {       /* 20 bytes */
     uint8_t  dmac[6];              /* written to the Ether header's bytes 0..5 */
@@ -1220,6 +1220,120 @@ int pkt_fwd_host(const pkt_fwd_adj_t *adj, uint32_t nadj, const pkt_batch_t *bat
                  uint32_t which_ip, uint32_t flags, pkt_lpm_t *lpm, const uint32_t *nexthop,
                  const uint8_t *select, uint8_t *status, uint32_t *port, uint32_t *adj_index,
                  uint64_t *hits, uint64_t *bytes);
+
+/* ---- IPv4 fragmentation of a batch to a per-packet MTU ----
+ * What a router does with the packets pkt_fwd_batch leaves at PKT_FWD_MTU: one source packet becomes one or several
+ * output packets, packed into a second slab, with the chain columns the following calls need (a second parse would
+ * walk a non-first fragment's payload as an L4 header).  The reference defines nothing here, so this header fixes the
+ * semantics; they follow RFC 791's fragmentation procedure and RFC 1624 for the checksum.
+ *
+ * pkt_frag_batch, per source packet i: the first test that applies gives status[i].
+ *  1. select != NULL && select[i] == 0: PKT_FRAG_SKIPPED.
+ *  2. The IP entry is found exactly as in pkt_flow_key_batch / pkt_lpm_lookup_batch / pkt_fwd_batch: which_ip
+ *     (PKT_FLOW_LAST included) counts the IPv4 and IPv6 entries together over min(n_hdrs, PKT_MAX_HDRS) entries; a
+ *     which_ip in 16..0xFE is refused.  No such entry: PKT_FRAG_NO_IP.  Its 20 / 40 bytes not inside the packet's
+ *     length (under the pkt_batch_t clamp rules): PKT_FRAG_SPAN.
+ *  3. m = mtu ? mtu[i] : mtu_all (mtu_all > 65535 is refused).  L is pkt_fwd_batch's L3 length: bytes 2..3 of an IPv4
+ *     entry, or 40 + bytes 4..5 of an IPv6 entry.  m == 0 || L <= m: PKT_FRAG_FITS, with no other header check:
+ *     FITS is exactly "step 6 of pkt_fwd_batch would not say PKT_FWD_MTU".
+ *  4. An IPv6 entry: PKT_FRAG_IPV6 (routers do not fragment IPv6).
+ *  5. Byte 0 != 0x45, or L < 20: PKT_FRAG_BAD_HDR (IPv4 options are out of scope; the walk does not model them).
+ *  6. ip_off + L > the packet's length: PKT_FRAG_TRUNC.
+ *  7. Byte 6 & 0x40: PKT_FRAG_DF.
+ *  8. m < 28: PKT_FRAG_MTU (not even 8 payload bytes fit).
+ *  9. per = (m - 20) & ~7, P = L - 20, k = ceil(P / per), w = bytes 6..7 big-endian, o = w & 0x1FFF.
+ *     o + (k - 1) * per / 8 > 0x1FFF: PKT_FRAG_BAD_HDR.
+ * 10. PKT_FRAG_SPLIT with nfrag = k (k >= 2, because L > m).
+ * Outputs per source packet: FITS gives 1 (0 with PKT_FRAG_ONLY_SPLIT), SPLIT gives k, every other status 0.
+ * nfrag[i] is that count, first[i] the index of its first output, or PKT_FRAG_NONE when nfrag[i] == 0.  Outputs are
+ * ordered by (i, j): source order, then fragment order; the result is exact and the same from run to run.
+ * A FITS output is the packet's bytes [0, len_i) verbatim, trailing padding included.  Fragment j of a SPLIT packet is
+ *  - the source bytes [0, ip_off) verbatim: the L2 prefix and any outer headers.  When which_ip selects an inner
+ *    header the outer headers' length fields (outer IP total length, UDP length) are NOT corrected: that is the
+ *    caller's to fix (pkt_set_fields_csum);
+ *  - the 20-byte IP header, the source's with bytes 2..3 = 20 + the slice's length; bytes 6..7 = (w & 0xC000) | MF |
+ *    (o + j * per / 8), MF = 0x2000 for j < k - 1 and w & 0x2000 for the last fragment (a fragment of a fragment keeps
+ *    its more-fragments bit); bytes 10..11 = HC', updated incrementally over the two changed words, pkt_fwd_batch's
+ *    way: s = (~HC & 0xFFFF) + (~L & 0xFFFF) + L' + (~w & 0xFFFF) + w', folded twice, HC' = ~s & 0xFFFF.  This is not
+ *    Packet::ipv4_checksum: a checksum that was wrong stays wrong by the same amount;
+ *  - payload bytes [j * per, min((j + 1) * per, P)) of the datagram.  Source bytes past ip_off + L (Ethernet padding)
+ *    go nowhere.
+ * Layout of dst: output q starts at out_off[q]; out_off[0] = 0 and out_off[q + 1] = out_off[q] + round_up(out_len[q],
+ * 16); exactly the bytes [out_off[q], out_off[q] + round_up(out_len[q], 16)) are written: the packet, then zeros.  dst
+ * is 16-byte aligned, never read, and must not overlap the source slab.  *bytes_out_total is the sum of the rounded
+ * lengths, *n_out the number of outputs; nothing at or past *bytes_out_total is written.  Entries q in [*n_out,
+ * out_cap) of the per-output arrays are written as empty (out_off 0, out_len 0, src_index PKT_FRAG_NONE, frag_index 0,
+ * out_chain->n_hdrs 0), so the out_cap-sized arrays are at once an indexed pkt_batch_t of out_cap packets with an
+ * empty tail, and out_chain is slot-major over it (columns strided by out_cap).  src_index, frag_index and each
+ * out_chain column may be NULL (out_chain itself too).
+ * out_chain: a FITS output gets the source's rows j < min(n_hdrs, PKT_MAX_HDRS) and that n_hdrs; a fragment gets the
+ * rows up to and including the IP entry (index e), n_hdrs = e + 1: the bytes before the IP header are copied
+ * verbatim, so the offsets hold, and the entries after it describe bytes a fragment may not have.  Later rows are not
+ * written.  pkt_fwd_batch, pkt_flow_key_batch (fragments key without ports), pkt_lpm_lookup_batch and pkt_pcap_write
+ * take the result with no second parse.
+ * Overflow: if *n_out > out_cap, *n_out >= 2^32 or *bytes_out_total > dst_len, the call (or pkt_frag_result) returns
+ * PKT_ERR_INVALID_ARG with both totals set: the capacity to retry with.  The decision is taken on the device, as in
+ * pkt_pcap_write, and the writing kernels exit: dst and the per-output arrays (and first) are unspecified, but nothing
+ * outside their capacities is written; status / nfrag / hits stay valid.  With PKT_FRAG_NO_WRITE dst, out_cap and the
+ * per-output arrays are ignored and may be NULL / 0: only status, nfrag, first, hits and the totals are produced.  That
+ * is the sizing pass, and it never overflows (first is meaningful while *n_out < 2^32).
+ * hits: device uint64_t[PKT_FRAG_STATUS_COUNT], 8-byte aligned, ADDED to as pkt_fwd_batch's is; exact, every call adds
+ * exactly n.  status, nfrag, first and hits may each be NULL.
+ *  - PKT_ERR_INVALID_ARG before any launch, with a text starting "pkt_frag" in pkt_ctx_last_error:
+ *    pkt_flow_key_batch's batch and slab rules; a NULL chain, or a NULL chain column with n > 0; n >= 2^32; a bad
+ *    which_ip; unknown flag bits; mtu_all > 65535; a misaligned dst (16), hits (8), out_off (8) or mtu (2); without
+ *    PKT_FRAG_NO_WRITE a NULL dst, out_off or out_len, or out_cap == 0 or >= 2^32; a second call on the ctx before
+ *    pkt_frag_result (the one-in-flight rule of pkt_pcap_write_async).  n == 0 succeeds with both totals 0 and
+ *    writes the empty tail.
+ *  - pkt_frag_batch waits for the two totals (one host wait); pkt_frag_batch_async queues the same kernels and
+ *    pkt_frag_result takes the totals and the overflow verdict.  Scratch lives in the ctx and grows on demand.
+ *  - On the device: a decision kernel (a lane owns a source packet; per tile of 256 the outputs and rounded bytes;
+ *    per-status counts merged per block in LDS), a one-block scan that also decides the overflow, an emit kernel (a
+ *    packet's rows are closed-form from per and P; a wave spreads the rows of its 64 packets over its lanes, so a
+ *    packet of 8190 fragments costs its rows, not a loop in one lane) and a copy kernel (a wave walks 64 outputs'
+ *    16-byte chunks together; each chunk is built in registers from the aligned source chunks that hold its bytes and
+ *    stored whole).  No lane waits for another; no global atomics but the hits adds.
+ * pkt_frag_host is the same operation on HOST pointers: no ctx, no device; the slab's and dst's alignment rules hold
+ * for dst, hits, out_off and mtu and are waived for the slab.
+ * Out of scope: ICMP fragmentation-needed / packet-too-big generation (PKT_FRAG_DF and PKT_FRAG_IPV6 are its inputs);
+ * reassembly; IPv4 options; fixing outer tunnel lengths. */
+typedef enum pkt_frag_status {
+    PKT_FRAG_FITS    = 0, /* one output: the packet, whole */
+    PKT_FRAG_SPLIT   = 1, /* nfrag >= 2 outputs */
+    PKT_FRAG_SKIPPED = 2, /* select[i] == 0 */
+    PKT_FRAG_NO_IP   = 3, /* the chain has no such IPv4 / IPv6 entry */
+    PKT_FRAG_SPAN    = 4, /* the IP entry's 20 / 40 bytes are not inside the packet */
+    PKT_FRAG_IPV6    = 5, /* an IPv6 packet above the mtu: routers do not fragment it */
+    PKT_FRAG_BAD_HDR = 6, /* byte 0 != 0x45, total length < 20, or the last fragment's offset would not fit 13 bits */
+    PKT_FRAG_TRUNC   = 7, /* the datagram's total length does not lie inside the packet */
+    PKT_FRAG_DF      = 8, /* don't-fragment is set */
+    PKT_FRAG_MTU     = 9  /* mtu < 28: not even 8 payload bytes fit */
+} pkt_frag_status_t;
+#define PKT_FRAG_STATUS_COUNT 10
+#define PKT_FRAG_ONLY_SPLIT 1u          /* flags: a FITS packet gives no output */
+#define PKT_FRAG_NO_WRITE   2u          /* flags: decide and total everything, store no packet byte and no per-output array */
+#define PKT_FRAG_NONE       0xFFFFFFFFu /* first[i] / src_index[q] when there is none */
+int pkt_frag_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                   uint32_t flags, const uint16_t *mtu, uint32_t mtu_all, const uint8_t *select,
+                   uint8_t *status, uint32_t *nfrag, uint32_t *first,
+                   uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                   uint64_t *out_off, uint32_t *out_len, uint32_t *src_index, uint16_t *frag_index,
+                   const pkt_chain_t *out_chain,
+                   uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out, void *stream);
+int pkt_frag_batch_async(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                         uint32_t flags, const uint16_t *mtu, uint32_t mtu_all, const uint8_t *select,
+                         uint8_t *status, uint32_t *nfrag, uint32_t *first,
+                         uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                         uint64_t *out_off, uint32_t *out_len, uint32_t *src_index, uint16_t *frag_index,
+                         const pkt_chain_t *out_chain, uint64_t *hits, void *stream);
+int pkt_frag_result(pkt_ctx_t *ctx, uint64_t *bytes_out_total, uint64_t *n_out);
+int pkt_frag_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                  uint32_t flags, const uint16_t *mtu, uint32_t mtu_all, const uint8_t *select,
+                  uint8_t *status, uint32_t *nfrag, uint32_t *first,
+                  uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                  uint64_t *out_off, uint32_t *out_len, uint32_t *src_index, uint16_t *frag_index,
+                  const pkt_chain_t *out_chain,
+                  uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
 
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);

@@ -1,7 +1,7 @@
 // pktgpu_ctx.hpp — the pkt_ctx behind the C ABI's opaque handle and the internal entry points the sources
 // share: the kernel sources (pktgpu.hip: parse; pktgpu_rewrite.hip: getters, to_vec, setters; pktgpu_pcap.hip /
 // pktgpu_pcapw.hip: pcap indexer / writer; pktgpu_compare.hip, pktgpu_edit.hip, pktgpu_l4csum.hip, pktgpu_flow.hip, pktgpu_match.hip,
-// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_gen.hip, pktgpu_gather.hip) and the
+// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_gen.hip, pktgpu_gather.hip) and the
 // host-only ones (pktgpu_ctx.cpp: lifecycle and knobs; pktgpu_hostpath.cpp: host-memory paths; pktgpu_mgpu.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -88,6 +88,14 @@ struct PcapWriteScratch : QueuedResult {
     uint64_t dst_len = 0;         // the last queued write's capacity (total > dst_len = it did not fit)
 };
 
+// Scratch of pkt_frag_batch (pktgpu_frag.hip), grown on demand: the totals' device words, the tile sums, the
+// per-packet plans and the per-output columns the caller did not ask for.  Its result words: [total rounded
+// bytes, outputs, nonzero = they did not fit]; pending: a call queued by pkt_frag_batch_async.
+struct FragScratch : QueuedResult {
+    void* buf = nullptr;
+    uint64_t bytes = 0;
+};
+
 // Scratch of pkt_compare_batch (pktgpu_compare.hip): 256 slots of four device words the blocks add
 // their counts to (equal, len, bytes; the lowest bad index as the maximum of its complement), all zero
 // between calls, and the pinned words their sums are copied to: [n_equal, n_len, n_bytes, first_bad
@@ -135,6 +143,7 @@ struct pkt_ctx {
     HostPipe hp;
     PcapScratch pc;
     PcapWriteScratch pw;
+    FragScratch fr;
     CompareScratch cmp;
     MaxScratch mx;
     uint32_t window = 0;  // 0 = auto

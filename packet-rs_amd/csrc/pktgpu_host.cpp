@@ -10,6 +10,7 @@
 #include "pktgpu_dispatch.hpp"
 #include "pktgpu_lpm.hpp"
 #include "pktgpu_fwd.hpp"
+#include "pktgpu_frag.hpp"
 
 namespace {
 
@@ -1029,6 +1030,111 @@ int pkt_fwd_host(const pkt_fwd_adj_t* adj, uint32_t nadj, const pkt_batch_t* b, 
         if (adj_index) adj_index[i] = out_adj;
         if (hits) hits[st] += 1;
         if (bytes) bytes[st] += len;
+    }
+    return PKT_SUCCESS;
+}
+
+// ---- pkt_frag_batch on host pointers (the CPU twin of pktgpu_frag.hip): two sequential passes over the packets with
+// the decision, the fragment header and the refusals of pktgpu_frag.hpp, which the kernels share.  The first pass
+// decides and totals; the second, when the outputs fit, writes them a byte at a time.
+namespace {
+
+FragPlan frag_plan_host(const BatchSrc& src, const pkt_chain_t* chain, uint64_t n, uint64_t i, uint32_t which_ip,
+                        uint32_t flags, const uint16_t* mtu, uint32_t mtu_all, const uint8_t* select) {
+    const uint64_t off = pkt_off(src, i);
+    FragPlan p{};
+    p.len = pkt_len(src, i, off);
+    p.st = PKT_FRAG_SKIPPED;
+    if (select && !select[i]) return p;
+    uint32_t nh = chain->n_hdrs[i];
+    nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+    FragFind f;
+    for (uint32_t j = 0; j < nh; j++) frag_find_step(f, which_ip, j, chain->hdr_type[j * n + i], chain->hdr_off[j * n + i]);
+    p.st = frag_find_status(f, p.len);
+    if (p.st != PKT_FRAG_FITS) return p;
+    const uint8_t* ip = src.slab + off + f.ipo;
+    uint32_t h[3];
+    for (uint32_t k = 0; k < 3; k++) h[k] = ip[4 * k] | (uint32_t)ip[4 * k + 1] << 8 | (uint32_t)ip[4 * k + 2] << 16 | (uint32_t)ip[4 * k + 3] << 24;
+    frag_decide(p, f.ipt, f.ipo, p.len, h, mtu ? mtu[i] : mtu_all);
+    frag_finish(p, f, nh, flags);
+    return p;
+}
+
+}  // namespace
+
+int pkt_frag_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags, const uint16_t* mtu,
+                  uint32_t mtu_all, const uint8_t* select, uint8_t* status, uint32_t* nfrag, uint32_t* first, uint8_t* dst,
+                  uint64_t dst_len, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len, uint32_t* src_index,
+                  uint16_t* frag_index, const pkt_chain_t* out_chain, uint64_t* hits, uint64_t* bytes_out_total,
+                  uint64_t* n_out) {
+    if (bytes_out_total) *bytes_out_total = 0;
+    if (n_out) *n_out = 0;
+    if (frag_call_error(b, chain, which_ip, flags, mtu, mtu_all, dst, out_cap, out_off, out_len, hits, false))
+        return PKT_ERR_INVALID_ARG;
+    const uint64_t n = b->n;
+    const bool write = !(flags & PKT_FRAG_NO_WRITE);
+    const BatchSrc src = batch_src(b);
+    uint64_t q = 0, bytes = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const FragPlan p = frag_plan_host(src, chain, n, i, which_ip, flags, mtu, mtu_all, select);
+        if (status) status[i] = (uint8_t)p.st;
+        if (nfrag) nfrag[i] = p.nout;
+        if (first) first[i] = p.nout ? (uint32_t)q : PKT_FRAG_NONE;
+        if (hits) hits[p.st] += 1;
+        q += p.nout;
+        bytes += frag_out_bytes(p);
+    }
+    if (bytes_out_total) *bytes_out_total = bytes;
+    if (n_out) *n_out = q;
+    if (!write) return PKT_SUCCESS;
+    if (frag_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
+    uint8_t* oc_nh = out_chain ? const_cast<uint8_t*>(out_chain->n_hdrs) : nullptr;
+    uint8_t* oc_ty = out_chain ? const_cast<uint8_t*>(out_chain->hdr_type) : nullptr;
+    uint16_t* oc_of = out_chain ? const_cast<uint16_t*>(out_chain->hdr_off) : nullptr;
+    q = 0;
+    uint64_t pos = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const FragPlan p = frag_plan_host(src, chain, n, i, which_ip, flags, mtu, mtu_all, select);
+        if (!p.nout) continue;
+        const uint8_t* s = src.slab + pkt_off(src, i);
+        uint32_t h[3] = {0, 0, 0};
+        if (p.st == PKT_FRAG_SPLIT)
+            for (uint32_t k = 0; k < 3; k++) {
+                const uint8_t* ip = s + p.ipo + 4 * k;
+                h[k] = ip[0] | (uint32_t)ip[1] << 8 | (uint32_t)ip[2] << 16 | (uint32_t)ip[3] << 24;
+            }
+        for (uint32_t j = 0; j < p.nout; j++, q++) {
+            const uint32_t ol = frag_out_len(p, j);
+            uint8_t* d = dst + pos;
+            if (p.st == PKT_FRAG_SPLIT) {
+                const uint32_t he = p.ipo + 20u;
+                memcpy(d, s, he);
+                uint32_t o[3];
+                frag_header(p, j, h, o);
+                for (uint32_t k = 0; k < 12; k++) d[p.ipo + k] = (uint8_t)(o[k >> 2] >> (8u * (k & 3u)));
+                memcpy(d + he, s + he + (uint64_t)j * p.per, ol - he);
+            } else if (ol) {
+                memcpy(d, s, ol);
+            }
+            memset(d + ol, 0, frag_round16(ol) - ol);
+            out_off[q] = pos;
+            out_len[q] = ol;
+            if (src_index) src_index[q] = (uint32_t)i;
+            if (frag_index) frag_index[q] = (uint16_t)j;
+            if (oc_nh) oc_nh[q] = (uint8_t)p.nh;
+            for (uint32_t r = 0; r < p.nh; r++) {
+                if (oc_ty) oc_ty[r * out_cap + q] = chain->hdr_type[r * n + i];
+                if (oc_of) oc_of[r * out_cap + q] = chain->hdr_off[r * n + i];
+            }
+            pos += frag_round16(ol);
+        }
+    }
+    for (; q < out_cap; q++) {
+        out_off[q] = 0;
+        out_len[q] = 0;
+        if (src_index) src_index[q] = PKT_FRAG_NONE;
+        if (frag_index) frag_index[q] = 0;
+        if (oc_nh) oc_nh[q] = 0;
     }
     return PKT_SUCCESS;
 }

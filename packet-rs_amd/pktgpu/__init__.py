@@ -25,7 +25,7 @@ from . import schema
 from .schema import (ABI_VERSION, DEPTH_LIMIT, ENTRIES, ENTRY_ID, GROUPS, HDR_ID, HDR_NAMES,  # noqa: F401
                      HDR_SIZES, MAX_HDRS, OK, STATUS_NAMES, TRUNCATED)
 
-__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "Forwarder", "fwd_adjacencies", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
+__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "Forwarder", "fwd_adjacencies", "FragResult", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
 
 
 def resolve_columns(columns):
@@ -754,6 +754,19 @@ class Parser:
         action one of schema.FWD_ACT_FORWARD / _DROP / _PUNT, or a numpy array of schema.FWD_ADJ_DTYPE
         (pkt_fwd_adj_t).  host=True gives the host form (pkt_fwd_host: numpy arrays in and out, no device)."""
         return Forwarder(None if host else self, adj)
+
+    def fragment(self, batch, chain, mtu=1500, select=None, which_ip=0, only_split=False, plan_only=False,
+                 out_cap=None, dst_bytes=None, hits=None, host=False, stream=None):
+        """pkt_frag_batch: every packet whose L3 length is above its mtu becomes IPv4 fragments, every other packet
+        that may pass goes through whole, all packed at 16-byte-aligned offsets of a new slab -> FragResult.  `mtu`: one
+        number for the batch, or a uint16 [n] array (0 = no limit).  `select` (uint8 [n]): a packet whose byte is 0 is
+        skipped.  `which_ip` as Lpm.lookup takes it.  only_split: a packet that fits gives no output.  plan_only: the
+        sizing pass (PKT_FRAG_NO_WRITE): status, nfrag, first and the totals alone.  out_cap / dst_bytes: the
+        capacities; without them a sizing pass runs first (one more host wait).  hits: True allocates zeroed uint64
+        [10] per-status counters, an array passed in is accumulated into.  `batch` / `chain`: the forms Lpm.lookup
+        takes.  host=True is pkt_frag_host: numpy arrays in and out, no device."""
+        return _fragment(self, batch, chain, mtu, select, which_ip, only_split, plan_only, out_cap, dst_bytes, hits, host,
+                         stream)
 
     def reorder(self, perm, slab=None, stride=None, n=None, offsets=None, lens=None, columns=None, start=None,
                 nseg=None, slot=None, m=None, out=None, stream=None):
@@ -1778,6 +1791,109 @@ class Forwarder:
             self.close()
         except Exception:
             pass
+
+
+(FRAG_FITS, FRAG_SPLIT, FRAG_SKIPPED, FRAG_NO_IP, FRAG_SPAN, FRAG_IPV6, FRAG_BAD_HDR, FRAG_TRUNC, FRAG_DF,
+ FRAG_MTU) = range(10)
+FRAG_NONE, FRAG_ONLY_SPLIT, FRAG_NO_WRITE = schema.FRAG_NONE, schema.FRAG_ONLY_SPLIT, schema.FRAG_NO_WRITE
+
+
+class FragResult:
+    """What Parser.fragment gives.  Per source packet: status (uint8: pktgpu.FRAG_FITS / _SPLIT / _SKIPPED / _NO_IP /
+    _SPAN / _IPV6 / _BAD_HDR / _TRUNC / _DF / _MTU), nfrag, first (uint32; FRAG_NONE where nfrag is 0).  The totals:
+    n_out, bytes_out.  Unless plan_only, per output (arrays of out_cap entries, empty past n_out): slab, offsets,
+    lens, src_index, frag_index and out_chain ({"n_hdrs", "hdr_type", "hdr_off"}, slot-major over out_cap); batch()
+    is the output as the batch dict the other calls take.  hits: the per-status counters, if asked for."""
+
+    def __init__(self, **kw):
+        self.slab = self.offsets = self.lens = self.src_index = self.frag_index = self.out_chain = self.hits = None
+        self.__dict__.update(kw)
+
+    def batch(self):
+        return dict(slab=self.slab, offsets=self.offsets, lens=self.lens)
+
+
+def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only, out_cap, dst_bytes, hits, host, stream):
+    from . import _lib
+    L = _lib.load()
+    if isinstance(batch, (tuple, list)):
+        batch = dict(zip(("slab", "offsets", "lens"), batch))
+    g = lambda k: batch.get(k)  # noqa: E731
+    nc = schema.FRAG_STATUS_COUNT
+    if host:
+        b, keep = _host_batch(_lib, batch)
+        cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                np.ascontiguousarray(chain["hdr_off"], np.uint16))
+        ch = _lib.PktChain(*[c.ctypes.data for c in cols])
+        select = None if select is None else np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+        empty = lambda k, dt: np.zeros(k, dt)  # noqa: E731
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
+        if not np.isscalar(mtu):
+            mtu = np.ascontiguousarray(mtu, np.uint16)
+    else:
+        torch = _torch()
+        b = parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
+        ch = parser._chain(chain)
+        dev = parser.torch_device
+        assert select is None or (select.is_cuda and select.dtype == torch.uint8 and select.is_contiguous()
+                                  and select.numel() >= b.n)
+        empty = lambda k, dt: torch.zeros(k, dtype=_tdtype(dt), device=dev)  # noqa: E731
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
+        if not isinstance(mtu, (int, np.integer)):
+            assert mtu.is_cuda and mtu.dtype == torch.uint16 and mtu.is_contiguous() and mtu.numel() >= b.n
+    per_pkt = not isinstance(mtu, (int, np.integer))
+    if hits is True:
+        hits = empty(nc, np.uint64)
+    if hits is not None and hits is not False:
+        assert ok(hits), f"fragment: hits is a contiguous uint64 [{nc}] array"
+    else:
+        hits = None
+    n = b.n
+    res = FragResult(status=empty(n, np.uint8), nfrag=empty(n, np.uint32), first=empty(n, np.uint32), hits=hits)
+    flags = schema.FRAG_ONLY_SPLIT if only_split else 0
+    tot, cnt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def call(fl, out, with_hits):
+        dst, cap = out.get("slab"), out.get("cap", 0)
+        oc = None
+        if out:
+            oc = _lib.PktChain(*[ptr(out["out_chain"][k]) for k in ("n_hdrs", "hdr_type", "hdr_off")])
+        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), fl, ptr(mtu) if per_pkt else None,
+                0 if per_pkt else int(mtu), ptr(select), ptr(res.status), ptr(res.nfrag), ptr(res.first),
+                dst.ctypes.data if host and dst is not None else dst.data_ptr() if dst is not None else None,
+                0 if dst is None else int(dst.size if host else dst.numel()), cap, ptr(out.get("offsets")), ptr(out.get("lens")),
+                ptr(out.get("src_index")), ptr(out.get("frag_index")), ctypes.byref(oc) if oc is not None else None,
+                ptr(hits) if with_hits else None, ctypes.byref(tot), ctypes.byref(cnt))
+        if host:
+            return L.pkt_frag_host(*args)
+        return L.pkt_frag_batch(parser._ctx, *args, parser._stream(stream))
+
+    def done(rc, what):
+        if rc == 0:
+            return
+        if host:
+            raise ValueError(f"pkt_frag_host failed ({rc}); it needs {cnt.value} outputs and {tot.value} bytes")
+        parser._check(rc, what)
+
+    sized = out_cap is not None and dst_bytes is not None
+    if plan_only or not sized:
+        done(call(flags | schema.FRAG_NO_WRITE, {}, plan_only), "pkt_frag_batch")
+        if plan_only:
+            res.n_out, res.bytes_out = cnt.value, tot.value
+            return res
+        out_cap = cnt.value if out_cap is None else out_cap
+        dst_bytes = tot.value if dst_bytes is None else dst_bytes
+    cap = max(1, int(out_cap))
+    out = dict(slab=empty(max(16, int(dst_bytes)), np.uint8), cap=cap, offsets=empty(cap, np.uint64),
+               lens=empty(cap, np.uint32), src_index=empty(cap, np.uint32), frag_index=empty(cap, np.uint16),
+               out_chain=dict(n_hdrs=empty(cap, np.uint8), hdr_type=empty((schema.MAX_HDRS, cap), np.uint8),
+                              hdr_off=empty((schema.MAX_HDRS, cap), np.uint16)))
+    done(call(flags, out, True), "pkt_frag_batch")
+    out.pop("cap")
+    res.__dict__.update(out, n_out=cnt.value, bytes_out=tot.value)
+    return res
 
 
 # ----------------------------------------------------------------- PacketSlice-style host views

@@ -59,6 +59,15 @@ FWD_KEEP_L2 = 1        # flags: no Ether entry is looked for, no MAC is written
 FWD_NO_WRITE = 2       # flags: decide everything, store nothing into the slab
 FWD_MAX_ADJ = 1 << 20
 
+# pkt_frag_* (IPv4 fragmentation to a per-packet MTU)
+(FRAG_FITS, FRAG_SPLIT, FRAG_SKIPPED, FRAG_NO_IP, FRAG_SPAN, FRAG_IPV6, FRAG_BAD_HDR, FRAG_TRUNC, FRAG_DF,
+ FRAG_MTU) = range(10)
+FRAG_STATUS = ["FITS", "SPLIT", "SKIPPED", "NO_IP", "SPAN", "IPV6", "BAD_HDR", "TRUNC", "DF", "MTU"]
+FRAG_STATUS_COUNT = 10
+FRAG_ONLY_SPLIT = 1      # flags: a FITS packet gives no output
+FRAG_NO_WRITE = 2        # flags: decide and total everything, store no packet byte and no per-output array
+FRAG_NONE = 0xFFFFFFFF   # first[i] / src_index[q] when there is none
+
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
                            ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])
