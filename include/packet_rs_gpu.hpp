@@ -411,6 +411,28 @@ class Parser {
         return t;
     }
 
+    // IPv4 reassembly of a batch's fragments (pkt_reasm_batch), the inverse of fragment: the fragments are grouped by
+    // (src, dst, protocol, identification) and every datagram that is complete in this batch is joined into one packet
+    // at the place of its last-arriving member; packets that are no fragments go through whole.  dst, out_off /
+    // out_len and out_chain are as fragment's; status[i] == PKT_REASM_PENDING marks the fragments to carry over to
+    // the next batch, out_index[i] is the output carrying packet i.  With PKT_REASM_NO_WRITE in `flags` only status /
+    // out_index / hits and the totals are produced.  Waits for the totals.
+    FragTotals reassemble(const pkt_batch_t& b, const pkt_chain_t& chain, uint8_t* dst, uint64_t dst_len, uint64_t out_cap,
+                          uint64_t* out_off, uint32_t* out_len, const pkt_chain_t* out_chain = nullptr,
+                          uint32_t* src_index = nullptr, uint32_t* nfrag = nullptr, uint8_t* status = nullptr,
+                          uint32_t* out_index = nullptr, const uint8_t* select = nullptr, uint32_t which_ip = 0,
+                          uint32_t flags = 0, uint64_t* hits = nullptr, hipStream_t s = nullptr) {
+        FragTotals t;
+        const int rc = pkt_reasm_batch(ctx_, &b, &chain, which_ip, flags, select, status, out_index, dst, dst_len, out_cap,
+                                       out_off, out_len, src_index, nfrag, out_chain, hits, &t.bytes, &t.n_out, s);
+        if (rc == PKT_ERR_INVALID_ARG && (t.n_out || t.bytes)) {
+            t.fits = false;
+            return t;
+        }
+        check(rc, ctx_, "pkt_reasm_batch");
+        return t;
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

@@ -1296,7 +1296,7 @@ int pkt_fwd_host(const pkt_fwd_adj_t *adj, uint32_t nadj, const pkt_batch_t *bat
  * pkt_frag_host is the same operation on HOST pointers: no ctx, no device; the slab's and dst's alignment rules hold
  * for dst, hits, out_off and mtu and are waived for the slab.
  * Out of scope: ICMP fragmentation-needed / packet-too-big generation (PKT_FRAG_DF and PKT_FRAG_IPV6 are its inputs);
- * reassembly; IPv4 options; fixing outer tunnel lengths. */
+ * reassembly (pkt_reasm_batch, below); IPv4 options; fixing outer tunnel lengths. */
 typedef enum pkt_frag_status {
     PKT_FRAG_FITS    = 0, /* one output: the packet, whole */
     PKT_FRAG_SPLIT   = 1, /* nfrag >= 2 outputs */
@@ -1334,6 +1334,106 @@ int pkt_frag_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t w
                   uint64_t *out_off, uint32_t *out_len, uint32_t *src_index, uint16_t *frag_index,
                   const pkt_chain_t *out_chain,
                   uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
+
+/* ---- IPv4 reassembly of a batch's fragments ----
+ * The inverse of pkt_frag_batch: the fragments of a batch (or of a stream window) are grouped by datagram and joined
+ * into whole packets in a second slab, which is an indexed batch again: pkt_parse_batch, pkt_l4_checksum_batch,
+ * pkt_flow_key_batch, pkt_match_batch and pkt_pcap_write take it.  The reference defines nothing here, so this header
+ * fixes the semantics; they follow RFC 791's reassembly, with overlaps refused rather than merged (as RFC 5722 does
+ * for IPv6 and Linux does for IPv4).
+ *
+ * pkt_reasm_batch, per source packet i: the first test that applies gives status[i].
+ *  1. select != NULL && select[i] == 0: PKT_REASM_SKIPPED.
+ *  2. The IP entry is found exactly as in pkt_frag_batch step 2 (which_ip, PKT_FLOW_LAST included, over min(n_hdrs,
+ *     PKT_MAX_HDRS) entries; a which_ip in 16..0xFE is refused).  No such entry: PKT_REASM_NO_IP.  Its 20 / 40 bytes
+ *     not inside the packet's length (under the pkt_batch_t clamp rules): PKT_REASM_SPAN.
+ *  3. The entry is IPv6, or IPv4 with (bytes 6..7 & 0x3FFF) == 0 (pkt_l4_checksum_batch's fragment test):
+ *     PKT_REASM_WHOLE, with no other header check.  (The IPv6 fragment extension header is out of scope.)
+ *  4. It is an IPv4 fragment.  L = bytes 2..3, w = bytes 6..7 (big-endian), s = 8 * (w & 0x1FFF), len = L - 20,
+ *     e = s + len.  Byte 0 != 0x45, or L <= 20 (an empty fragment), or MF (w & 0x2000) set and len % 8 != 0:
+ *     PKT_REASM_BAD_HDR.
+ *  5. ip_off + L > the packet's length: PKT_REASM_TRUNC.
+ *  6. Otherwise the packet is a MEMBER of the datagram with the key (src, dst, protocol, identification) = (bytes
+ *     12..15, 16..19, 9, 4..5).  Nothing else belongs to the key: VLAN tags, outer headers and ip_off may differ
+ *     between members.  Every member of a datagram gets the datagram's verdict.
+ * The verdict of a datagram is defined on the set of its members in this batch, whatever their order:
+ *  - PKT_REASM_JOINED iff exactly one member has MF clear, and the members, sorted by s and each used exactly once,
+ *    tile [0, E): s_0 = 0, s_(k+1) = e_k, and the last in that order is the MF-clear member, with e = E;
+ *  - PKT_REASM_TOO_BIG if that tiling holds but 20 + E > 65535;
+ *  - PKT_REASM_PENDING otherwise: a hole, a duplicate, any overlap, two final fragments, a fragment past the end.
+ * A SKIPPED, BAD_HDR or TRUNC packet is not a member; its datagram is then usually PENDING.
+ * Outputs: WHOLE gives one output, the packet's bytes [0, len_i) verbatim as PKT_FRAG_FITS does (none with
+ * PKT_REASM_ONLY_JOINED).  A JOINED datagram gives one output, owned by its member with the LARGEST source index: a
+ * reassembler emits a datagram when its last fragment arrives, so the output keeps its causal place among the whole
+ * packets.  Every other status gives none.  Outputs are ordered by owner index.  out_index[i] is the output that
+ * carries packet i's bytes, the same value for every member of a datagram, PKT_REASM_NONE where there is none.
+ * src_index[q] is the owner, nfrag[q] the number of source packets in output q (1 for WHOLE).  The result is exact and
+ * byte-identical from run to run.
+ * A joined output is
+ *  - bytes [0, ip_off0 + 20) of the member with s = 0 (ip_off0: its ip_off), where bytes 2..3 of the IP header = 20 + E,
+ *    bytes 6..7 = w0 & 0xC000, and bytes 10..11 are updated incrementally over those two words (RFC 1624 eq. 3, folded
+ *    twice, exactly as pkt_frag_batch's fragment header: a checksum that was wrong stays wrong by the same amount);
+ *  - then every member's payload, its own bytes [ip_off_m + 20, ip_off_m + L_m), at ip_off0 + 20 + s_m.
+ * Source bytes past a member's ip_off + L go nowhere.  When which_ip selects an inner header the outer headers' length
+ * fields are NOT corrected (pkt_frag_batch's caveat).
+ * Layout of dst, out_off / out_len, the 16-byte rounding with zero fill, the empty tail up to out_cap (out_off 0,
+ * out_len 0, src_index PKT_REASM_NONE, nfrag 0, out_chain->n_hdrs 0), *bytes_out_total, *n_out, hits (device
+ * uint64_t[PKT_REASM_STATUS_COUNT], ADDED to, exactly n per call), the overflow return (PKT_ERR_INVALID_ARG with both
+ * totals, decided on the device; out_index is then unspecified too) and PKT_REASM_NO_WRITE as the sizing pass (only
+ * status, out_index, hits and the totals) are pkt_frag_batch's.  status, out_index, src_index, nfrag, hits, out_chain
+ * and each of its columns may be NULL.
+ * out_chain: a WHOLE output gets the source's rows j < min(n_hdrs, PKT_MAX_HDRS) and that n_hdrs; a joined output gets
+ * the s = 0 member's rows up to and including the IP entry (index e), n_hdrs = e + 1, as a fragment gets from
+ * pkt_frag_batch.  The L4 header of a joined datagram is not walked here: pkt_parse_batch over the output batch gives
+ * the full chain, now correctly.
+ *  - PKT_ERR_INVALID_ARG before any launch, with a text starting "pkt_reasm" in pkt_ctx_last_error: pkt_frag_batch's
+ *    refusals without the mtu ones; a second call on the ctx before pkt_reasm_result (the one-in-flight rule).
+ *    n == 0 succeeds with both totals 0 and writes the empty tail.
+ *  - pkt_reasm_batch waits for the two totals (one host wait); pkt_reasm_batch_async queues the same kernels and
+ *    pkt_reasm_result takes the totals and the overflow verdict.  Scratch lives in the ctx and grows on demand.
+ *  - On the device the cost is linear in n: classify (a lane owns a source packet), group (an open-addressed table of
+ *    >= 2 n slots; one compare-and-swap per probed slot, adds and a max into the datagram's words, and the fragment
+ *    start put into a second table used as a set), link (every MF-set member looks its end up in that set; a miss is a
+ *    hole), count, a one-block scan that also decides the overflow, emit, and a source-driven copy.  No lane waits for
+ *    another; the only loops over shared state are probe sequences bounded by the slot count; no atomics on packet
+ *    bytes, and every destination byte is written exactly once.
+ * pkt_reasm_host is the same operation on HOST pointers: no ctx, no device; the alignment rules hold for dst, hits and
+ * out_off and are waived for the slab.
+ * Out of scope: state across batches and timeouts (status == PKT_REASM_PENDING is the mask to carry fragments over
+ * with, through pkt_reorder_batch or `select`); IPv6 fragment headers; IPv4 options; merging overlaps. */
+typedef enum pkt_reasm_status {
+    PKT_REASM_WHOLE   = 0, /* not a fragment: one output, the packet, whole */
+    PKT_REASM_JOINED  = 1, /* a member of a datagram that is complete in this batch */
+    PKT_REASM_PENDING = 2, /* a member of a datagram that is not (a hole, a duplicate, an overlap, two finals) */
+    PKT_REASM_SKIPPED = 3, /* select[i] == 0 */
+    PKT_REASM_NO_IP   = 4, /* the chain has no such IPv4 / IPv6 entry */
+    PKT_REASM_SPAN    = 5, /* the IP entry's 20 / 40 bytes are not inside the packet */
+    PKT_REASM_BAD_HDR = 6, /* a fragment with byte 0 != 0x45, no payload, or MF and a length that is no multiple of 8 */
+    PKT_REASM_TRUNC   = 7, /* the fragment's total length does not lie inside the packet */
+    PKT_REASM_TOO_BIG = 8  /* the members tile a datagram of more than 65535 bytes */
+} pkt_reasm_status_t;
+#define PKT_REASM_STATUS_COUNT 9
+#define PKT_REASM_ONLY_JOINED 1u          /* flags: a WHOLE packet gives no output */
+#define PKT_REASM_NO_WRITE    2u          /* flags: decide and total everything, store no packet byte and no per-output array */
+#define PKT_REASM_NONE        0xFFFFFFFFu /* out_index[i] / src_index[q] when there is none */
+int pkt_reasm_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                    uint32_t flags, const uint8_t *select, uint8_t *status, uint32_t *out_index,
+                    uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                    uint64_t *out_off, uint32_t *out_len, uint32_t *src_index, uint32_t *nfrag,
+                    const pkt_chain_t *out_chain,
+                    uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out, void *stream);
+int pkt_reasm_batch_async(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                          uint32_t flags, const uint8_t *select, uint8_t *status, uint32_t *out_index,
+                          uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                          uint64_t *out_off, uint32_t *out_len, uint32_t *src_index, uint32_t *nfrag,
+                          const pkt_chain_t *out_chain, uint64_t *hits, void *stream);
+int pkt_reasm_result(pkt_ctx_t *ctx, uint64_t *bytes_out_total, uint64_t *n_out);
+int pkt_reasm_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                   uint32_t flags, const uint8_t *select, uint8_t *status, uint32_t *out_index,
+                   uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                   uint64_t *out_off, uint32_t *out_len, uint32_t *src_index, uint32_t *nfrag,
+                   const pkt_chain_t *out_chain,
+                   uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
 
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);

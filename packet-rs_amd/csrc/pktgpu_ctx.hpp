@@ -1,7 +1,8 @@
 // pktgpu_ctx.hpp — the pkt_ctx behind the C ABI's opaque handle and the internal entry points the sources
 // share: the kernel sources (pktgpu.hip: parse; pktgpu_rewrite.hip: getters, to_vec, setters; pktgpu_pcap.hip /
 // pktgpu_pcapw.hip: pcap indexer / writer; pktgpu_compare.hip, pktgpu_edit.hip, pktgpu_l4csum.hip, pktgpu_flow.hip, pktgpu_match.hip,
-// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_gen.hip, pktgpu_gather.hip) and the
+// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_reasm.hip, pktgpu_gen.hip,
+// pktgpu_gather.hip) and the
 // host-only ones (pktgpu_ctx.cpp: lifecycle and knobs; pktgpu_hostpath.cpp: host-memory paths; pktgpu_mgpu.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -96,6 +97,15 @@ struct FragScratch : QueuedResult {
     uint64_t bytes = 0;
 };
 
+// Scratch of pkt_reasm_batch (pktgpu_reasm.hip), grown on demand: the totals' device words, the tile sums, the
+// per-packet records, the datagrams' words, the two open-addressed tables and src_index when the caller did not ask
+// for it.  Its result words: [total rounded bytes, outputs, nonzero = they did not fit]; pending: a call queued by
+// pkt_reasm_batch_async.
+struct ReasmScratch : QueuedResult {
+    void* buf = nullptr;
+    uint64_t bytes = 0;
+};
+
 // Scratch of pkt_compare_batch (pktgpu_compare.hip): 256 slots of four device words the blocks add
 // their counts to (equal, len, bytes; the lowest bad index as the maximum of its complement), all zero
 // between calls, and the pinned words their sums are copied to: [n_equal, n_len, n_bytes, first_bad
@@ -144,6 +154,7 @@ struct pkt_ctx {
     PcapScratch pc;
     PcapWriteScratch pw;
     FragScratch fr;
+    ReasmScratch rs;
     CompareScratch cmp;
     MaxScratch mx;
     uint32_t window = 0;  // 0 = auto

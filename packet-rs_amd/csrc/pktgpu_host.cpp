@@ -1,7 +1,10 @@
 // pktgpu_host.cpp — host-side part of the C ABI: metadata tables, the pcap indexer and the
 // host checksum.  No device code.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <new>
+#include <vector>
 
 #include "../../include/pktgpu.h"
 #include "pktgpu_batch.hpp"
@@ -11,6 +14,7 @@
 #include "pktgpu_lpm.hpp"
 #include "pktgpu_fwd.hpp"
 #include "pktgpu_frag.hpp"
+#include "pktgpu_reasm.hpp"
 
 namespace {
 
@@ -1137,6 +1141,186 @@ int pkt_frag_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which
         if (oc_nh) oc_nh[q] = 0;
     }
     return PKT_SUCCESS;
+}
+
+// ---- pkt_reasm_batch on host pointers (the CPU twin of pktgpu_reasm.hip).  The classification, the joined header and
+// the refusals are pktgpu_reasm.hpp's, which the kernels share; the grouping is NOT the kernels': the members are
+// sorted by (key, s) and each datagram is walked fragment by fragment, which is the tiling of include/pktgpu.h as it
+// is written.  The kernels reach the same verdict from five words per datagram (reasm_verdict), so a device run that
+// equals this one checks that rule too.
+namespace {
+
+ReasmRec reasm_rec_host(const BatchSrc& src, const pkt_chain_t* chain, uint64_t n, uint64_t i, uint32_t which_ip,
+                        const uint8_t* select) {
+    const uint64_t off = pkt_off(src, i);
+    ReasmRec r{};
+    r.plen = pkt_len(src, i, off);
+    r.st = PKT_REASM_SKIPPED;
+    if (select && !select[i]) return r;
+    uint32_t nh = chain->n_hdrs[i];
+    nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+    FragFind f;
+    for (uint32_t j = 0; j < nh; j++) frag_find_step(f, which_ip, j, chain->hdr_type[j * n + i], chain->hdr_off[j * n + i]);
+    r.st = reasm_find_status(f, r.plen);
+    if (r.st != PKT_REASM_WHOLE) return r;
+    const uint8_t* ip = src.slab + off + f.ipo;
+    uint32_t h[5];
+    for (uint32_t k = 0; k < 5; k++) h[k] = ip[4 * k] | (uint32_t)ip[4 * k + 1] << 8 | (uint32_t)ip[4 * k + 2] << 16 | (uint32_t)ip[4 * k + 3] << 24;
+    reasm_classify(r, f, nh, h);
+    return r;
+}
+
+struct ReasmGroup {  // a datagram: its members are order[lo, hi), sorted by s
+    uint64_t lo, hi;
+    uint32_t owner, E;
+};
+
+int reasm_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags, const uint8_t* select,
+               uint8_t* status, uint32_t* out_index, uint8_t* dst, uint64_t dst_len, uint64_t out_cap, uint64_t* out_off,
+               uint32_t* out_len, uint32_t* src_index, uint32_t* nfrag, const pkt_chain_t* out_chain, uint64_t* hits,
+               uint64_t* bytes_out_total, uint64_t* n_out) {
+    const uint64_t n = b->n;
+    const bool write = !(flags & PKT_REASM_NO_WRITE);
+    const BatchSrc src = batch_src(b);
+    std::vector<ReasmRec> rec(n);
+    std::vector<uint32_t> order;  // the members
+    for (uint64_t i = 0; i < n; i++) {
+        rec[i] = reasm_rec_host(src, chain, n, i, which_ip, select);
+        if (rec[i].member) order.push_back((uint32_t)i);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const ReasmRec &p = rec[x], &q = rec[y];
+        if (p.src != q.src) return p.src < q.src;
+        if (p.dst != q.dst) return p.dst < q.dst;
+        if (p.idp != q.idp) return p.idp < q.idp;
+        if (p.s != q.s) return p.s < q.s;
+        return x < y;
+    });
+    std::vector<ReasmGroup> groups;
+    std::vector<uint32_t> gof(n);  // a member's datagram
+    for (uint64_t lo = 0, hi; lo < order.size(); lo = hi) {
+        const ReasmRec& first = rec[order[lo]];
+        for (hi = lo + 1; hi < order.size(); hi++) {
+            const ReasmRec& r = rec[order[hi]];
+            if (!reasm_same_key(first.src, first.dst, first.idp, r.src, r.dst, r.idp)) break;
+        }
+        // the walk: s_0 = 0, s_(k+1) = e_k, one final member, and it is the last
+        uint32_t finals = 0, owner = 0, at = 0;
+        bool tiled = true;
+        for (uint64_t k = lo; k < hi; k++) {
+            const ReasmRec& r = rec[order[k]];
+            tiled = tiled && r.s == at;
+            at = r.s + r.len;
+            finals += r.mf ? 0u : 1u;
+            owner = order[k] > owner ? order[k] : owner;
+        }
+        const ReasmRec& last = rec[order[hi - 1]];
+        const uint32_t E = last.s + last.len;
+        const uint32_t verdict = !(tiled && finals == 1u && !last.mf) ? PKT_REASM_PENDING
+                                 : 20u + E > 65535u                  ? PKT_REASM_TOO_BIG
+                                                                     : PKT_REASM_JOINED;
+        for (uint64_t k = lo; k < hi; k++) {
+            rec[order[k]].st = verdict;
+            gof[order[k]] = (uint32_t)groups.size();
+        }
+        groups.push_back(ReasmGroup{lo, hi, owner, E});
+    }
+    // the outputs, in owner order
+    std::vector<uint32_t> oq(n, PKT_REASM_NONE);
+    uint64_t q = 0, bytes = 0;
+    auto out_len_of = [&](uint64_t i) -> uint32_t {
+        const ReasmRec& r = rec[i];
+        if (r.st == PKT_REASM_WHOLE) return flags & PKT_REASM_ONLY_JOINED ? 0u : r.plen;
+        if (r.st != PKT_REASM_JOINED || groups[gof[i]].owner != i) return 0u;
+        return rec[order[groups[gof[i]].lo]].ipo + 20u + groups[gof[i]].E;
+    };
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t ol = out_len_of(i);
+        if (!ol) continue;
+        oq[i] = (uint32_t)q++;
+        bytes += frag_round16(ol);
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t st = rec[i].st;
+        if (status) status[i] = (uint8_t)st;
+        if (out_index) out_index[i] = st == PKT_REASM_JOINED ? oq[groups[gof[i]].owner] : oq[i];
+        if (hits) hits[st] += 1;
+    }
+    if (bytes_out_total) *bytes_out_total = bytes;
+    if (n_out) *n_out = q;
+    if (!write) return PKT_SUCCESS;
+    if (frag_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
+    uint8_t* oc_nh = out_chain ? const_cast<uint8_t*>(out_chain->n_hdrs) : nullptr;
+    uint8_t* oc_ty = out_chain ? const_cast<uint8_t*>(out_chain->hdr_type) : nullptr;
+    uint16_t* oc_of = out_chain ? const_cast<uint16_t*>(out_chain->hdr_off) : nullptr;
+    uint64_t pos = 0;
+    q = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t ol = out_len_of(i);
+        if (!ol) continue;
+        uint8_t* d = dst + pos;
+        uint64_t rows_of = i;
+        uint32_t members = 1;
+        if (rec[i].st == PKT_REASM_WHOLE) {
+            memcpy(d, src.slab + pkt_off(src, i), ol);
+        } else {
+            const ReasmGroup& g = groups[gof[i]];
+            rows_of = order[g.lo];
+            members = (uint32_t)(g.hi - g.lo);
+            const uint32_t ipo0 = rec[rows_of].ipo;
+            const uint8_t* s0 = src.slab + pkt_off(src, rows_of);
+            memcpy(d, s0, ipo0 + 20u);
+            uint32_t h[3], o[3];
+            for (uint32_t k = 0; k < 3; k++) {
+                const uint8_t* ip = s0 + ipo0 + 4 * k;
+                h[k] = ip[0] | (uint32_t)ip[1] << 8 | (uint32_t)ip[2] << 16 | (uint32_t)ip[3] << 24;
+            }
+            reasm_header(g.E, h, o);
+            for (uint32_t k = 0; k < 12; k++) d[ipo0 + k] = (uint8_t)(o[k >> 2] >> (8u * (k & 3u)));
+            for (uint64_t k = g.lo; k < g.hi; k++) {
+                const ReasmRec& m = rec[order[k]];
+                memcpy(d + ipo0 + 20u + m.s, src.slab + pkt_off(src, order[k]) + m.ipo + 20u, m.len);
+            }
+        }
+        memset(d + ol, 0, frag_round16(ol) - ol);
+        out_off[q] = pos;
+        out_len[q] = ol;
+        if (src_index) src_index[q] = (uint32_t)i;
+        if (nfrag) nfrag[q] = members;
+        const uint32_t nh = rec[rows_of].nh;
+        if (oc_nh) oc_nh[q] = (uint8_t)nh;
+        for (uint32_t r = 0; r < nh; r++) {
+            if (oc_ty) oc_ty[r * out_cap + q] = chain->hdr_type[r * n + rows_of];
+            if (oc_of) oc_of[r * out_cap + q] = chain->hdr_off[r * n + rows_of];
+        }
+        pos += frag_round16(ol);
+        q++;
+    }
+    for (; q < out_cap; q++) {
+        out_off[q] = 0;
+        out_len[q] = 0;
+        if (src_index) src_index[q] = PKT_REASM_NONE;
+        if (nfrag) nfrag[q] = 0;
+        if (oc_nh) oc_nh[q] = 0;
+    }
+    return PKT_SUCCESS;
+}
+
+}  // namespace
+
+int pkt_reasm_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags, const uint8_t* select,
+                   uint8_t* status, uint32_t* out_index, uint8_t* dst, uint64_t dst_len, uint64_t out_cap, uint64_t* out_off,
+                   uint32_t* out_len, uint32_t* src_index, uint32_t* nfrag, const pkt_chain_t* out_chain, uint64_t* hits,
+                   uint64_t* bytes_out_total, uint64_t* n_out) {
+    if (bytes_out_total) *bytes_out_total = 0;
+    if (n_out) *n_out = 0;
+    if (reasm_call_error(b, chain, which_ip, flags, dst, out_cap, out_off, out_len, hits, false)) return PKT_ERR_INVALID_ARG;
+    try {
+        return reasm_host(b, chain, which_ip, flags, select, status, out_index, dst, dst_len, out_cap, out_off, out_len,
+                          src_index, nfrag, out_chain, hits, bytes_out_total, n_out);
+    } catch (const std::bad_alloc&) {  // the twin keeps O(n) host memory
+        return PKT_ERR_UNSUPPORTED;
+    }
 }
 
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,

@@ -25,7 +25,7 @@ from . import schema
 from .schema import (ABI_VERSION, DEPTH_LIMIT, ENTRIES, ENTRY_ID, GROUPS, HDR_ID, HDR_NAMES,  # noqa: F401
                      HDR_SIZES, MAX_HDRS, OK, STATUS_NAMES, TRUNCATED)
 
-__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "Forwarder", "fwd_adjacencies", "FragResult", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
+__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "Forwarder", "fwd_adjacencies", "FragResult", "ReasmResult","match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
 
 
 def resolve_columns(columns):
@@ -767,6 +767,20 @@ class Parser:
         takes.  host=True is pkt_frag_host: numpy arrays in and out, no device."""
         return _fragment(self, batch, chain, mtu, select, which_ip, only_split, plan_only, out_cap, dst_bytes, hits, host,
                          stream)
+
+    def reassemble(self, batch, chain, select=None, which_ip=0, only_joined=False, plan_only=False, out_cap=None,
+                   dst_bytes=None, hits=None, host=False, stream=None):
+        """pkt_reasm_batch, the inverse of fragment: the IPv4 fragments of the batch are grouped by (src, dst, protocol,
+        identification) and every datagram that is complete in this batch is joined into one packet, at the place of
+        its last-arriving fragment; packets that are no fragments go through whole -> ReasmResult, whose batch() the
+        other calls take (parse it again for the joined datagrams' full chains).  `select` (uint8 [n]): a packet whose
+        byte is 0 is skipped.  `which_ip` as Lpm.lookup takes it.  only_joined: a whole packet gives no output.
+        plan_only: the sizing pass (PKT_REASM_NO_WRITE): status, out_index and the totals alone.  out_cap /
+        dst_bytes: the capacities; without them a sizing pass runs first (one more host wait).  hits: True allocates
+        zeroed uint64 [9] per-status counters, an array passed in is accumulated into.  `batch` / `chain`: the forms
+        Lpm.lookup takes.  host=True is pkt_reasm_host: numpy arrays in and out, no device."""
+        return _reassemble(self, batch, chain, select, which_ip, only_joined, plan_only, out_cap, dst_bytes, hits, host,
+                           stream)
 
     def reorder(self, perm, slab=None, stride=None, n=None, offsets=None, lens=None, columns=None, start=None,
                 nseg=None, slot=None, m=None, out=None, stream=None):
@@ -1891,6 +1905,109 @@ def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only
                out_chain=dict(n_hdrs=empty(cap, np.uint8), hdr_type=empty((schema.MAX_HDRS, cap), np.uint8),
                               hdr_off=empty((schema.MAX_HDRS, cap), np.uint16)))
     done(call(flags, out, True), "pkt_frag_batch")
+    out.pop("cap")
+    res.__dict__.update(out, n_out=cnt.value, bytes_out=tot.value)
+    return res
+
+
+(REASM_WHOLE, REASM_JOINED, REASM_PENDING, REASM_SKIPPED, REASM_NO_IP, REASM_SPAN, REASM_BAD_HDR, REASM_TRUNC,
+ REASM_TOO_BIG) = range(9)
+REASM_NONE, REASM_ONLY_JOINED, REASM_NO_WRITE = schema.REASM_NONE, schema.REASM_ONLY_JOINED, schema.REASM_NO_WRITE
+
+
+class ReasmResult:
+    """What Parser.reassemble gives.  Per source packet: status (uint8: pktgpu.REASM_WHOLE / _JOINED / _PENDING /
+    _SKIPPED / _NO_IP / _SPAN / _BAD_HDR / _TRUNC / _TOO_BIG) and out_index (uint32: the output carrying the packet's
+    bytes; REASM_NONE where there is none).  The totals: n_out, bytes_out.  Unless plan_only, per output (arrays of
+    out_cap entries, empty past n_out): slab, offsets, lens, src_index (the owner: the last-arriving member), nfrag
+    and out_chain ({"n_hdrs", "hdr_type", "hdr_off"}, slot-major over out_cap); batch() is the output as the batch
+    dict the other calls take.  pending: the mask of the fragments to carry over to the next batch.  hits: the
+    per-status counters, if asked for."""
+
+    def __init__(self, **kw):
+        self.slab = self.offsets = self.lens = self.src_index = self.nfrag = self.out_chain = self.hits = None
+        self.__dict__.update(kw)
+
+    def batch(self):
+        return dict(slab=self.slab, offsets=self.offsets, lens=self.lens)
+
+    @property
+    def pending(self):
+        return self.status == REASM_PENDING
+
+
+def _reassemble(parser, batch, chain, select, which_ip, only_joined, plan_only, out_cap, dst_bytes, hits, host, stream):
+    from . import _lib
+    L = _lib.load()
+    if isinstance(batch, (tuple, list)):
+        batch = dict(zip(("slab", "offsets", "lens"), batch))
+    g = lambda k: batch.get(k)  # noqa: E731
+    nc = schema.REASM_STATUS_COUNT
+    if host:
+        b, keep = _host_batch(_lib, batch)
+        cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                np.ascontiguousarray(chain["hdr_off"], np.uint16))
+        ch = _lib.PktChain(*[c.ctypes.data for c in cols])
+        select = None if select is None else np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+        empty = lambda k, dt: np.zeros(k, dt)  # noqa: E731
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
+    else:
+        torch = _torch()
+        b = parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
+        ch = parser._chain(chain)
+        dev = parser.torch_device
+        assert select is None or (select.is_cuda and select.dtype == torch.uint8 and select.is_contiguous()
+                                  and select.numel() >= b.n)
+        empty = lambda k, dt: torch.zeros(k, dtype=_tdtype(dt), device=dev)  # noqa: E731
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
+    if hits is True:
+        hits = empty(nc, np.uint64)
+    if hits is not None and hits is not False:
+        assert ok(hits), f"reassemble: hits is a contiguous uint64 [{nc}] array"
+    else:
+        hits = None
+    n = b.n
+    res = ReasmResult(status=empty(n, np.uint8), out_index=empty(n, np.uint32), hits=hits)
+    flags = schema.REASM_ONLY_JOINED if only_joined else 0
+    tot, cnt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def call(fl, out, with_hits):
+        dst, cap = out.get("slab"), out.get("cap", 0)
+        oc = None
+        if out:
+            oc = _lib.PktChain(*[ptr(out["out_chain"][k]) for k in ("n_hdrs", "hdr_type", "hdr_off")])
+        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), fl, ptr(select), ptr(res.status), ptr(res.out_index),
+                dst.ctypes.data if host and dst is not None else dst.data_ptr() if dst is not None else None,
+                0 if dst is None else int(dst.size if host else dst.numel()), cap, ptr(out.get("offsets")), ptr(out.get("lens")),
+                ptr(out.get("src_index")), ptr(out.get("nfrag")), ctypes.byref(oc) if oc is not None else None,
+                ptr(hits) if with_hits else None, ctypes.byref(tot), ctypes.byref(cnt))
+        if host:
+            return L.pkt_reasm_host(*args)
+        return L.pkt_reasm_batch(parser._ctx, *args, parser._stream(stream))
+
+    def done(rc, what):
+        if rc == 0:
+            return
+        if host:
+            raise ValueError(f"pkt_reasm_host failed ({rc}); it needs {cnt.value} outputs and {tot.value} bytes")
+        parser._check(rc, what)
+
+    sized = out_cap is not None and dst_bytes is not None
+    if plan_only or not sized:
+        done(call(flags | schema.REASM_NO_WRITE, {}, plan_only), "pkt_reasm_batch")
+        if plan_only:
+            res.n_out, res.bytes_out = cnt.value, tot.value
+            return res
+        out_cap = cnt.value if out_cap is None else out_cap
+        dst_bytes = tot.value if dst_bytes is None else dst_bytes
+    cap = max(1, int(out_cap))
+    out = dict(slab=empty(max(16, int(dst_bytes)), np.uint8), cap=cap, offsets=empty(cap, np.uint64),
+               lens=empty(cap, np.uint32), src_index=empty(cap, np.uint32), nfrag=empty(cap, np.uint32),
+               out_chain=dict(n_hdrs=empty(cap, np.uint8), hdr_type=empty((schema.MAX_HDRS, cap), np.uint8),
+                              hdr_off=empty((schema.MAX_HDRS, cap), np.uint16)))
+    done(call(flags, out, True), "pkt_reasm_batch")
     out.pop("cap")
     res.__dict__.update(out, n_out=cnt.value, bytes_out=tot.value)
     return res

@@ -260,6 +260,18 @@ SIGNATURES = {
                                      ctypes.c_uint32, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, ctypes.c_uint64,
                                      ctypes.c_uint64, _P, _P, _P, _P, ctypes.POINTER(PktChain), _P,
                                      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_reasm_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                       ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
+                                       ctypes.POINTER(PktChain), _P, ctypes.POINTER(ctypes.c_uint64),
+                                       ctypes.POINTER(ctypes.c_uint64), _P]),
+    "pkt_reasm_batch_async": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                             ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
+                                             _P, ctypes.POINTER(PktChain), _P, _P]),
+    "pkt_reasm_result": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_reasm_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                      ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
+                                      ctypes.POINTER(PktChain), _P, ctypes.POINTER(ctypes.c_uint64),
+                                      ctypes.POINTER(ctypes.c_uint64)]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),

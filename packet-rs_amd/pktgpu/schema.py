@@ -67,6 +67,14 @@ FRAG_STATUS_COUNT = 10
 FRAG_ONLY_SPLIT = 1      # flags: a FITS packet gives no output
 FRAG_NO_WRITE = 2        # flags: decide and total everything, store no packet byte and no per-output array
 FRAG_NONE = 0xFFFFFFFF   # first[i] / src_index[q] when there is none
+# pkt_reasm_* (IPv4 reassembly of a batch's fragments)
+(REASM_WHOLE, REASM_JOINED, REASM_PENDING, REASM_SKIPPED, REASM_NO_IP, REASM_SPAN, REASM_BAD_HDR, REASM_TRUNC,
+ REASM_TOO_BIG) = range(9)
+REASM_STATUS = ["WHOLE", "JOINED", "PENDING", "SKIPPED", "NO_IP", "SPAN", "BAD_HDR", "TRUNC", "TOO_BIG"]
+REASM_STATUS_COUNT = 9
+REASM_ONLY_JOINED = 1    # flags: a WHOLE packet gives no output
+REASM_NO_WRITE = 2       # flags: decide and total everything, store no packet byte and no per-output array
+REASM_NONE = 0xFFFFFFFF  # out_index[i] / src_index[q] when there is none
 
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
