@@ -433,6 +433,30 @@ class Parser {
         return t;
     }
 
+    // A pattern set compiled onto this context's device (pkt_scan_create): `pats[k]` is bytes[off, off + len) of
+    // `bytes`, 1..PKT_SCAN_MAX_LEN bytes, with its flags (PKT_SCAN_NOCASE), group and action.  The caller destroys it
+    // with pkt_scan_destroy after the calls queued on it.
+    pkt_scan_t* scanner(const std::vector<uint8_t>& bytes, const std::vector<pkt_scan_pattern_t>& pats,
+                        uint32_t default_action = 0) {
+        pkt_scan_t* t = nullptr;
+        check(pkt_scan_create(ctx_, bytes.empty() ? nullptr : bytes.data(), bytes.size(), pats.empty() ? nullptr : pats.data(),
+                              (uint32_t)pats.size(), default_action, &t), ctx_, "pkt_scan_create");
+        return t;
+    }
+
+    // Every packet's region searched for the set (pkt_scan_batch): PKT_SCAN_PAYLOAD is the bytes after every header of
+    // `chain`, PKT_SCAN_PACKET the whole packet (`chain` may be NULL).  status[i] (PKT_SCAN_HIT / _MISS / ...), pat[i] the
+    // lowest occurring pattern (PKT_SCAN_NONE: none), off[i] its first occurrence, action[i], sel[i] = action[i] != 0,
+    // count[i] all occurrences, matched[i] the groups; hits[npats + 1] is added to.  Each may be NULL.  Asynchronous on s.
+    static void scan(pkt_scan_t* t, const pkt_batch_t& b, const pkt_chain_t* chain, uint8_t* status, uint32_t* pat = nullptr,
+                     uint16_t* off = nullptr, uint32_t* action = nullptr, uint8_t* sel = nullptr, uint32_t* count = nullptr,
+                     uint64_t* matched = nullptr, uint64_t* hits = nullptr, uint32_t region = PKT_SCAN_PAYLOAD,
+                     const uint8_t* select = nullptr, hipStream_t s = nullptr) {
+        const int rc = pkt_scan_batch(t, &b, chain, region, select, status, pat, off, action, sel, count, matched, hits, s);
+        if (rc != PKT_SUCCESS)
+            throw std::runtime_error(std::string("pkt_scan_batch failed (") + std::to_string(rc) + "): " + pkt_scan_last_error(t));
+    }
+
    private:
     pkt_ctx_t* ctx_ = nullptr;
 };

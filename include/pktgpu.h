@@ -1435,6 +1435,94 @@ int pkt_reasm_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t 
                    const pkt_chain_t *out_chain,
                    uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
 
+/* ---- pkt_scan_*: multi-pattern byte search over a batch's payloads.  Every call above looks at headers; this one
+ * answers whether a packet's bytes contain one of a set of byte strings (signature prefilters, protocol
+ * identification by banner).  The reference defines nothing here, so this header fixes the semantics.  A pattern
+ * set is up to PKT_SCAN_MAX_PATTERNS byte strings of 1..PKT_SCAN_MAX_LEN bytes, PKT_SCAN_MAX_BYTES in all; it is
+ * compiled and uploaded once (pkt_scan_create) and searched by one kernel in a single pass over the packets' bytes.
+ *  - The region [r0, r1) of packet i: r1 is the packet's length under the pkt_batch_t clamp rules.
+ *    PKT_SCAN_PACKET: r0 = 0, and `chain` may be NULL.  PKT_SCAN_PAYLOAD: r0 is the first byte after every header of
+ *    the list, the MAXIMUM over j < min(n_hdrs, PKT_MAX_HDRS) of hdr_off[j] + pkt_hdr_size(hdr_type[j]) (not the
+ *    last entry: quirk Q2 puts a wire-earlier GRE option last); on a parse's chain that is its payload_off.
+ *    n_hdrs == 0: PKT_SCAN_NO_CHAIN.  A hdr_type outside 1..21, or r0 > r1: PKT_SCAN_SPAN.  r0 == r1 is a scanned
+ *    packet with no occurrence.
+ *  - An occurrence is a pair (p, s) with r0 <= s, s + len_p <= r1 and every pattern byte equal to the packet's
+ *    byte at its place; under PKT_SCAN_NOCASE both bytes are folded first (0x41..0x5A to 0x61..0x7A, nothing else
+ *    changes).  Occurrences overlap in any way; identical patterns each count; a prefix of another pattern counts
+ *    at the same s.  No byte outside [r0, r1) ever contributes: a string that straddles two packets of a packed
+ *    slab is no occurrence.
+ *  - Outputs, device [n] arrays, each may be NULL.  count[i]: the occurrences.  pat[i]: the lowest pattern index
+ *    with one, else PKT_SCAN_NONE.  off[i]: the smallest s of that pattern, from the packet's first byte (the
+ *    hdr_off convention), else 0.  matched[i]: bit g set iff a pattern of group g occurs.  action[i]: pattern
+ *    pat[i]'s action; default_action for a scanned packet with no occurrence and for NO_CHAIN and SPAN; 0 for
+ *    SKIPPED.  sel[i] = action[i] != 0 (the mask pkt_pcap_write and pkt_edit_batch take).  status[i]: HIT iff
+ *    count[i] > 0, MISS for a scanned packet without one.  select[i] == 0 gives SKIPPED.  A packet that is not
+ *    scanned has count 0, pat NONE, off 0, matched 0.
+ *  - hits: a device uint64_t[npats + 1], 8-byte aligned, caller-owned, ADDED to as pkt_match_batch's counters are:
+ *    hits[p] gains pattern p's occurrences, hits[npats] the number of MISS packets.  Exact: a call adds sum(count)
+ *    to hits[0..npats).  With every output NULL, or n == 0, the call succeeds, launches nothing and leaves the
+ *    counters untouched.
+ *  - pkt_scan_create validates, compiles on the host and uploads; blocking, and the only allocation (the
+ *    pkt_match_create pattern).  `bytes` and `pats` are HOST memory, captured at the call.  PKT_ERR_INVALID_ARG
+ *    with a text starting "pkt_scan" in pkt_ctx_last_error: npats > PKT_SCAN_MAX_PATTERNS, the lengths' sum >
+ *    PKT_SCAN_MAX_BYTES, a len of 0 or above PKT_SCAN_MAX_LEN, off + len > nbytes, an unknown flag bit, a group
+ *    above 63, a non-zero reserved, a NULL pointer with a non-zero count.  npats == 0 is legal: every scanned
+ *    packet is a MISS.  pkt_scan_info: what was built.  nstates: the states of the two tries (below), their roots
+ *    included.  table_bytes: the compiled image.  placement: PKT_SCAN_PLACE_GLOBAL (the first-level filter in LDS,
+ *    the deeper levels in device memory) or PKT_SCAN_PLACE_LDS (the whole automaton in LDS: sets whose deeper
+ *    levels fit the kernel's budget); a host handle reports PKT_SCAN_PLACE_GLOBAL.
+ *  - pkt_scan_batch is asynchronous on `stream`, keeps no per-call state in the handle and never writes the compiled
+ *    set: several calls on one handle may be in flight on different streams.  PKT_ERR_INVALID_ARG before any launch,
+ *    with a text starting "pkt_scan_batch" in pkt_scan_last_error: the batch and slab rules with their texts; a NULL
+ *    chain, or with n > 0 a NULL chain column, when region is PAYLOAD; an unknown region; n >= 2^32; matched or
+ *    hits not 8-byte aligned.  pkt_scan_destroy is the caller's to order after the calls in flight.
+ *  - The compiled set: two failureless tries (exact patterns; NOCASE patterns, folded, walked over folded bytes),
+ *    so mixing the two kinds never multiplies states.  A start position walks the patterns that begin there and
+ *    stops at the first byte none continues with.  Level 1 is a 256-entry table per trie and a bitmap over the first
+ *    two (folded) bytes; deeper edges sit in one open-addressed table keyed by (state, byte).  The kernel reads
+ *    whole aligned 16-byte chunks only: at most 15 bytes past a packet's end, never past round_up(slab + slab_len,
+ *    16).  Per-packet results are add / min / or reductions in LDS: identical from run to run.
+ * pkt_scan_create_host gives the same handle type on HOST memory (the pkt_lpm_create_host pattern): pkt_scan_batch
+ * then takes host pointers, ignores `stream`, and waives the slab's alignment.  Its create refusals' text:
+ * pkt_scan_last_error(NULL).
+ * Out of scope: regular expressions; patterns above 64 bytes; a per-occurrence event list; matches across packets
+ * (pkt_reasm_batch first, then scan). */
+#define PKT_SCAN_MAX_PATTERNS 8192
+#define PKT_SCAN_MAX_LEN      64          /* bytes per pattern, 1..64 */
+#define PKT_SCAN_MAX_BYTES    131072      /* sum of the patterns' lengths */
+#define PKT_SCAN_NONE         0xFFFFFFFFu /* pat[i] when nothing occurs */
+#define PKT_SCAN_NOCASE       1u          /* pattern flag: compare ASCII letters without case */
+enum { PKT_SCAN_PACKET = 0, PKT_SCAN_PAYLOAD = 1 };                                  /* region */
+enum { PKT_SCAN_MISS = 0, PKT_SCAN_HIT = 1, PKT_SCAN_SKIPPED = 2, PKT_SCAN_NO_CHAIN = 3, PKT_SCAN_SPAN = 4 }; /* status */
+enum { PKT_SCAN_PLACE_GLOBAL = 0, PKT_SCAN_PLACE_LDS = 1 };                          /* pkt_scan_info_t.placement */
+typedef struct pkt_scan_pattern {      /* 16 bytes */
+    uint32_t off;                      /* the pattern is bytes[off, off + len) of the blob given to create */
+    uint16_t len;                      /* 1..PKT_SCAN_MAX_LEN */
+    uint8_t  flags;                    /* PKT_SCAN_NOCASE or 0 */
+    uint8_t  group;                    /* 0..63: the bit of `matched` this pattern sets */
+    uint32_t action;                   /* caller-defined; 0 means "not selected" */
+    uint32_t reserved;                 /* 0 */
+} pkt_scan_pattern_t;
+typedef struct pkt_scan_info {         /* 24 bytes */
+    uint32_t npatterns;
+    uint32_t nstates;                  /* of both tries, their roots included */
+    uint32_t max_len;                  /* the longest pattern */
+    uint32_t placement;                /* PKT_SCAN_PLACE_* */
+    uint64_t table_bytes;              /* the compiled image */
+} pkt_scan_info_t;
+typedef struct pkt_scan pkt_scan_t;
+size_t pkt_sizeof_scan_pattern(void);
+int pkt_scan_create(pkt_ctx_t *ctx, const uint8_t *bytes, uint64_t nbytes, const pkt_scan_pattern_t *pats,
+                    uint32_t npats, uint32_t default_action, pkt_scan_t **s);
+int pkt_scan_create_host(const uint8_t *bytes, uint64_t nbytes, const pkt_scan_pattern_t *pats,
+                         uint32_t npats, uint32_t default_action, pkt_scan_t **s);
+int pkt_scan_info(const pkt_scan_t *s, pkt_scan_info_t *info);
+int pkt_scan_batch(pkt_scan_t *s, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t region,
+                   const uint8_t *select, uint8_t *status, uint32_t *pat, uint16_t *off, uint32_t *action,
+                   uint8_t *sel, uint32_t *count, uint64_t *matched, uint64_t *hits, void *stream);
+int pkt_scan_destroy(pkt_scan_t *s);
+const char *pkt_scan_last_error(const pkt_scan_t *s);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -15,6 +15,7 @@
 #include "pktgpu_fwd.hpp"
 #include "pktgpu_frag.hpp"
 #include "pktgpu_reasm.hpp"
+#include "pktgpu_scan.hpp"
 
 namespace {
 
@@ -956,6 +957,60 @@ int pkt_lpm_destroy(pkt_lpm_t* t) {
 }
 
 const char* pkt_lpm_last_error(const pkt_lpm_t* t) { return t ? t->err.c_str() : t_lpm_create_err.c_str(); }
+
+// ---- pkt_scan_*: the public calls (the device handle: pktgpu_scan.hip).  The compile, the walk, the refusals and the
+// host handle's loop are pktgpu_scan.hpp's, shared with the kernel.
+size_t pkt_sizeof_scan_pattern(void) { return sizeof(pkt_scan_pattern_t); }
+
+static thread_local std::string t_scan_create_err;  // pkt_scan_last_error(NULL): the thread's last failed create_host
+
+int pkt_scan_create_host(const uint8_t* bytes, uint64_t nbytes, const pkt_scan_pattern_t* pats, uint32_t npats,
+                         uint32_t default_action, pkt_scan_t** out) {
+    if (!out) {
+        t_scan_create_err = "pkt_scan_create_host: null argument";
+        return PKT_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    ScanImage img;
+    const int rc = scan_compile(bytes, nbytes, pats, npats, img, t_scan_create_err);
+    if (rc != PKT_SUCCESS) return rc;
+    pkt_scan* s = new pkt_scan;
+    s->info = img.info;
+    s->host_words.swap(img.words);
+    s->view = img.view(s->host_words.data(), default_action);
+    *out = s;
+    return PKT_SUCCESS;
+}
+
+int pkt_scan_info(const pkt_scan_t* s, pkt_scan_info_t* info) {
+    if (!s || !info) return PKT_ERR_INVALID_ARG;
+    *info = s->info;
+    return PKT_SUCCESS;
+}
+
+int pkt_scan_batch(pkt_scan_t* s, const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t region, const uint8_t* select,
+                   uint8_t* status, uint32_t* pat, uint16_t* off, uint32_t* action, uint8_t* sel, uint32_t* count,
+                   uint64_t* matched, uint64_t* hits, void* stream) {
+    if (!s) return PKT_ERR_INVALID_ARG;
+    if (const char* msg = scan_batch_error(b, chain, region, matched, hits, s->ops != nullptr)) return scan_fail(s, msg);
+    if (b->n == 0) return PKT_SUCCESS;
+    if (!status && !pat && !off && !action && !sel && !count && !matched && !hits) return PKT_SUCCESS;
+    const bool pay = region == PKT_SCAN_PAYLOAD;
+    const ScanCall c{batch_src(b), b->n, pay ? chain->n_hdrs : nullptr, pay ? chain->hdr_type : nullptr,
+                     pay ? chain->hdr_off : nullptr, region, select, status, pat, off, action, sel, count, matched, hits};
+    if (s->ops) return s->ops->run(s, c, stream);
+    scan_host_run(s->view, c);
+    return PKT_SUCCESS;
+}
+
+int pkt_scan_destroy(pkt_scan_t* s) {
+    if (!s) return PKT_ERR_INVALID_ARG;
+    const int rc = s->ops ? s->ops->destroy(s) : PKT_SUCCESS;
+    delete s;
+    return rc;
+}
+
+const char* pkt_scan_last_error(const pkt_scan_t* s) { return s ? s->err.c_str() : t_scan_create_err.c_str(); }
 
 // ---- pkt_fwd_batch on host pointers (the CPU twin of pktgpu_fwd.hip): a sequential loop over the packets with the
 // decision, the checksum arithmetic and the refusals of pktgpu_fwd.hpp, which the kernel shares; the packet's bytes

@@ -25,7 +25,7 @@ from . import schema
 from .schema import (ABI_VERSION, DEPTH_LIMIT, ENTRIES, ENTRY_ID, GROUPS, HDR_ID, HDR_NAMES,  # noqa: F401
                      HDR_SIZES, MAX_HDRS, OK, STATUS_NAMES, TRUNCATED)
 
-__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "Forwarder", "fwd_adjacencies", "FragResult", "ReasmResult","match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
+__all__ = ["Parser", "FlowTable", "MatchProgram", "Dispatcher", "Lpm", "lpm_routes", "Forwarder", "fwd_adjacencies", "FragResult", "ReasmResult", "Scanner", "ScanResult", "scan_patterns", "match", "dispatch", "reorder", "segments", "flow_keys", "packet_slice", "view", "PacketSlice", "HeaderSlice", "resolve_columns", "schema"]
 
 
 def resolve_columns(columns):
@@ -781,6 +781,15 @@ class Parser:
         Lpm.lookup takes.  host=True is pkt_reasm_host: numpy arrays in and out, no device."""
         return _reassemble(self, batch, chain, select, which_ip, only_joined, plan_only, out_cap, dst_bytes, hits, host,
                            stream)
+
+    def scanner(self, patterns, nocase=False, groups=None, actions=None, default=0, host=False):
+        """pkt_scan_create: compile a set of byte strings (bytes or str, 1..64 bytes each, at most 8192 of them and
+        131072 bytes in all) on this parser's device -> Scanner.  `nocase`: one bool for the set or one per pattern
+        (ASCII letters compare without case).  `groups`: one number 0..63 per pattern, the bit of "matched" it sets
+        (default 0).  `actions`: one uint32 per pattern (default 1); a packet's action is that of its lowest
+        occurring pattern, `default` where nothing occurs, and "sel" is action != 0.  host=True gives the host handle
+        (pkt_scan_create_host: numpy arrays in and out, no device)."""
+        return Scanner(None if host else self, patterns, nocase, groups, actions, default)
 
     def reorder(self, perm, slab=None, stride=None, n=None, offsets=None, lens=None, columns=None, start=None,
                 nseg=None, slot=None, m=None, out=None, stream=None):
@@ -2014,6 +2023,163 @@ def _reassemble(parser, batch, chain, select, which_ip, only_joined, plan_only, 
 
 
 # ----------------------------------------------------------------- PacketSlice-style host views
+(SCAN_MISS, SCAN_HIT, SCAN_SKIPPED, SCAN_NO_CHAIN, SCAN_SPAN) = range(5)
+SCAN_NONE, SCAN_NOCASE = schema.SCAN_NONE, schema.SCAN_NOCASE
+_SCAN_OUT = (("status", np.uint8), ("pat", np.uint32), ("off", np.uint16), ("action", np.uint32), ("sel", np.uint8),
+             ("count", np.uint32), ("matched", np.uint64))
+
+
+def scan_patterns(patterns, nocase=False, groups=None, actions=None):
+    """A pattern list as pkt_scan_create takes it: (blob, table) with `blob` a uint8 array of the patterns' bytes end
+    to end and `table` a C-contiguous array of schema.SCAN_PATTERN_DTYPE (pkt_scan_pattern_t).  `patterns`: an
+    iterable of bytes / str (UTF-8), or such a (blob, table) pair, which is passed through."""
+    if isinstance(patterns, tuple) and len(patterns) == 2 and isinstance(patterns[1], np.ndarray) \
+            and patterns[1].dtype == schema.SCAN_PATTERN_DTYPE:
+        return np.ascontiguousarray(patterns[0], np.uint8).reshape(-1), np.ascontiguousarray(patterns[1])
+    pats = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
+    n = len(pats)
+    per = lambda v, d: [d] * n if v is None else ([v] * n if np.isscalar(v) else list(v))  # noqa: E731
+    nc, gr, ac = per(nocase, False), per(groups, 0), per(actions, 1)
+    if not (len(nc) == len(gr) == len(ac) == n):
+        raise ValueError("scanner: nocase / groups / actions must have one entry per pattern")
+    tab = np.zeros(n, schema.SCAN_PATTERN_DTYPE)
+    lens = np.array([len(p) for p in pats], np.int64)
+    if n and (lens.max() > 0xFFFF or max(gr) > 0xFF or min(gr) < 0):
+        raise ValueError("scanner: a pattern's length or group does not fit pkt_scan_pattern_t")
+    tab["off"] = np.concatenate(([0], np.cumsum(lens)[:-1])) if n else 0
+    tab["len"] = lens
+    tab["flags"] = [schema.SCAN_NOCASE if x else 0 for x in nc]
+    tab["group"] = gr
+    tab["action"] = ac
+    return np.frombuffer(b"".join(pats), np.uint8), tab
+
+
+class ScanResult:
+    """What Scanner.run gives, the arrays asked for among: status (uint8: pktgpu.SCAN_MISS / _HIT / _SKIPPED /
+    _NO_CHAIN / _SPAN), pat (uint32: the lowest occurring pattern, SCAN_NONE = none), off (uint16: its first
+    occurrence, from the packet's first byte), action (uint32), sel (uint8: action != 0, the mask pcap_write and edit
+    take), count (uint32: all occurrences), matched (uint64: bit g = a pattern of group g occurs); hits (uint64
+    [npatterns + 1]: occurrences per pattern, then the MISS packets), if asked for.  The rest is None."""
+
+    def __init__(self, **kw):
+        self.status = self.pat = self.off = self.action = self.sel = self.count = self.matched = self.hits = None
+        self.__dict__.update(kw)
+
+    @property
+    def hit(self):
+        return self.status == SCAN_HIT
+
+
+class Scanner:
+    """pkt_scan_t: a compiled pattern set (Parser.scanner).  Scanner(parser, patterns) lives on the parser's device
+    and takes and gives device tensors; Scanner(None, patterns) is the host handle over numpy arrays (no device).
+
+        sc = p.scanner([b"GET /", b"POST /", "user-agent:"], nocase=[False, False, True], groups=[0, 0, 1])
+        r = sc.run(batch, chain)                     # ScanResult: the payloads, from a parse's chain
+        p.pcap_write(slab, offsets, lens, select=r.sel)
+    """
+
+    def __init__(self, parser, patterns, nocase=False, groups=None, actions=None, default=0):
+        from . import _lib
+        self._lib = _lib
+        self._L = _lib.load()
+        self.parser = parser
+        self.blob, self.table = scan_patterns(patterns, nocase, groups, actions)
+        self.default = int(default)
+        n = self.table.size
+        bp = self.blob.ctypes.data if self.blob.size else None
+        tp = self.table.ctypes.data if n else None
+        h = ctypes.c_void_p()
+        if parser is None:
+            rc = self._L.pkt_scan_create_host(bp, self.blob.size, tp, n, self.default, ctypes.byref(h))
+            if rc != 0:
+                msg = self._L.pkt_scan_last_error(None)
+                raise ValueError(f"pkt_scan_create_host failed ({rc}): {msg.decode() if msg else ''}")
+        else:
+            parser._check(self._L.pkt_scan_create(parser._ctx, bp, self.blob.size, tp, n, self.default, ctypes.byref(h)),
+                          "pkt_scan_create")
+        self._t = h
+
+    def __len__(self):
+        return int(self.table.size)
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self._L.pkt_scan_last_error(self._t)
+            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+    def run(self, batch, chain=None, region="payload", select=None,
+            want=("status", "pat", "off", "action", "sel", "count", "matched"), hits=None, stream=None):
+        """pkt_scan_batch: search every packet's region for the set -> ScanResult with the `want`ed arrays.  `region`:
+        "payload" (the bytes after every header of `chain`, the chain columns of a parse of the batch) or "packet"
+        (the whole packet; `chain` may be None).  `select` (uint8 [n]): a packet whose byte is 0 is skipped.  `hits`:
+        True allocates zeroed uint64 [npatterns + 1] counters, an array passed in is accumulated into.  `batch`: the
+        forms Lpm.lookup takes (a dict, PcapStream.batch()'s tuple), or a FragResult / ReasmResult.  Device tensors
+        for a device handle, numpy arrays for a host handle.  Asynchronous on `stream`."""
+        if hasattr(batch, "batch") and callable(batch.batch):
+            batch = batch.batch()
+        if isinstance(batch, (tuple, list)):
+            batch = dict(zip(("slab", "offsets", "lens"), batch))
+        bad = set(want) - {k for k, _ in _SCAN_OUT}
+        if bad:
+            raise ValueError(f"scanner: unknown outputs {sorted(bad)}")
+        reg = schema.SCAN_REGION[region] if isinstance(region, str) else int(region)
+        g = lambda k: batch.get(k)  # noqa: E731
+        host = self.parser is None
+        keep = []
+        ch = None
+        if host:
+            b, arrs = _host_batch(self._lib, batch)
+            keep.append(arrs)
+            if chain is not None:
+                cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                        np.ascontiguousarray(chain["hdr_off"], np.uint16))
+                keep.append(cols)
+                ch = self._lib.PktChain(*[c.ctypes.data for c in cols])
+            if select is not None:
+                select = np.ascontiguousarray(select, np.uint8)
+            res = {k: np.zeros(b.n, dt) for k, dt in _SCAN_OUT if k in want}
+            if hits is True:
+                hits = np.zeros(len(self) + 1, np.uint64)
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        else:
+            torch = _torch()
+            b = self.parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
+            if chain is not None:
+                ch = self.parser._chain(chain)
+            if select is not None:
+                assert select.is_cuda and select.dtype == torch.uint8 and select.numel() >= b.n
+            dev = self.parser.torch_device
+            res = {k: torch.empty(b.n, dtype=_tdtype(dt), device=dev) for k, dt in _SCAN_OUT if k in want}
+            if hits is True:
+                hits = torch.zeros(len(self) + 1, dtype=_tdtype(np.uint64), device=dev)
+            elif hits is not None:
+                assert hits.is_cuda and hits.element_size() == 8 and hits.numel() >= len(self) + 1
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        self._check(self._L.pkt_scan_batch(self._t, ctypes.byref(b), None if ch is None else ctypes.byref(ch), reg,
+                                           ptr(select), *[ptr(res.get(k)) for k, _ in _SCAN_OUT], ptr(hits),
+                                           None if host else self.parser._stream(stream)), "pkt_scan_batch")
+        return ScanResult(hits=hits, **res)
+
+    @property
+    def info(self):
+        """pkt_scan_info -> {"npatterns", "nstates", "max_len", "placement", "table_bytes"}."""
+        i = self._lib.PktScanInfo()
+        self._check(self._L.pkt_scan_info(self._t, ctypes.byref(i)), "pkt_scan_info")
+        return {k: int(getattr(i, k)) for k, _ in i._fields_}
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self._L.pkt_scan_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HeaderSlice:
     """A `<Hdr>Slice` (headers.rs:172-296): a name and a view of `len()` bytes of the packet.
     Field getters are generated from the header's make_header! table."""

@@ -83,6 +83,16 @@ class PktLpmRoute(ctypes.Structure):
                 ("zero", ctypes.c_uint16), ("nexthop", ctypes.c_uint32)]
 
 
+class PktScanPattern(ctypes.Structure):
+    _fields_ = [("off", ctypes.c_uint32), ("len", ctypes.c_uint16), ("flags", ctypes.c_uint8), ("group", ctypes.c_uint8),
+                ("action", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class PktScanInfo(ctypes.Structure):
+    _fields_ = [("npatterns", ctypes.c_uint32), ("nstates", ctypes.c_uint32), ("max_len", ctypes.c_uint32),
+                ("placement", ctypes.c_uint32), ("table_bytes", ctypes.c_uint64)]
+
+
 class PktLpmInfo(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint64) for k in ("routes_v4", "routes_v6", "nodes_v4", "nodes_v6", "depth_v4", "depth_v6",
                                                "bytes")]
@@ -272,6 +282,14 @@ SIGNATURES = {
                                       ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
                                       ctypes.POINTER(PktChain), _P, ctypes.POINTER(ctypes.c_uint64),
                                       ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_sizeof_scan_pattern": (ctypes.c_size_t, []),
+    "pkt_scan_create": (ctypes.c_int, [_P, _P, ctypes.c_uint64, _P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "pkt_scan_create_host": (ctypes.c_int, [_P, ctypes.c_uint64, _P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "pkt_scan_info": (ctypes.c_int, [_P, ctypes.POINTER(PktScanInfo)]),
+    "pkt_scan_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pkt_scan_destroy": (ctypes.c_int, [_P]),
+    "pkt_scan_last_error": (ctypes.c_char_p, [_P]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -355,6 +373,7 @@ def load():
             or L.pkt_sizeof_match_term() != ctypes.sizeof(PktMatchTerm) \
             or L.pkt_sizeof_match_rule() != ctypes.sizeof(PktMatchRule) \
             or L.pkt_sizeof_lpm_route() != ctypes.sizeof(PktLpmRoute) \
+            or L.pkt_sizeof_scan_pattern() != ctypes.sizeof(PktScanPattern) \
             or L.pkt_sizeof_fwd_adj() != ctypes.sizeof(PktFwdAdj):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L

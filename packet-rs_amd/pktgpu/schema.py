@@ -76,6 +76,18 @@ REASM_ONLY_JOINED = 1    # flags: a WHOLE packet gives no output
 REASM_NO_WRITE = 2       # flags: decide and total everything, store no packet byte and no per-output array
 REASM_NONE = 0xFFFFFFFF  # out_index[i] / src_index[q] when there is none
 
+# pkt_scan_*: limits, the pattern flag, regions, statuses, placements
+SCAN_MAX_PATTERNS = 8192
+SCAN_MAX_LEN = 64
+SCAN_MAX_BYTES = 131072
+SCAN_NONE = 0xFFFFFFFF  # pat[i] when nothing occurs
+SCAN_NOCASE = 1
+SCAN_PACKET, SCAN_PAYLOAD = range(2)
+SCAN_REGION = {"packet": SCAN_PACKET, "payload": SCAN_PAYLOAD}
+SCAN_MISS, SCAN_HIT, SCAN_SKIPPED, SCAN_NO_CHAIN, SCAN_SPAN = range(5)
+SCAN_STATUS = ["MISS", "HIT", "SKIPPED", "NO_CHAIN", "SPAN"]
+SCAN_PLACE_GLOBAL, SCAN_PLACE_LDS = range(2)
+
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
                            ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])
@@ -85,6 +97,9 @@ FLOW_RECORD_DTYPE = np.dtype([("key", FLOW_KEY_DTYPE), ("first", np.uint64), ("p
 # pkt_lpm_route_t as a numpy record
 LPM_ROUTE_DTYPE = np.dtype([("addr", np.uint8, 16), ("ipver", np.uint8), ("plen", np.uint8), ("zero", np.uint16),
                             ("nexthop", np.uint32)])
+# pkt_scan_pattern_t
+SCAN_PATTERN_DTYPE = np.dtype([("off", np.uint32), ("len", np.uint16), ("flags", np.uint8), ("group", np.uint8),
+                               ("action", np.uint32), ("reserved", np.uint32)])
 
 # pkt_fwd_adj_t as a numpy record
 FWD_ADJ_DTYPE = np.dtype([("dmac", np.uint8, 6), ("smac", np.uint8, 6), ("port", np.uint32), ("mtu", np.uint16),
