@@ -411,6 +411,31 @@ class Parser {
         return t;
     }
 
+    // ICMP / ICMPv6 errors for the packets a router refuses (pkt_icmp_err_batch): packet i's code is code[i] (or
+    // code_all when `code` is NULL), its reason map[code] (or the code itself when `map`, a HOST array of 256 bytes,
+    // is NULL), so pkt_fwd_batch's or pkt_frag_batch's status array is `code` as it is.  Every packet that may be
+    // answered gives one error packet (swapped MACs, a fresh IP header from `cfg`, the ICMP header, the quote), packed
+    // into dst as fragment packs its outputs; out_index[i] is packet i's output.  mtu[i] (or mtu_all) is what a
+    // too-big error reports.  With PKT_ICMPE_NO_WRITE in `flags` only status / out_index / hits and the totals are
+    // produced.  Waits for the totals.
+    FragTotals icmp_errors(const pkt_batch_t& b, const pkt_chain_t& chain, const pkt_icmp_cfg_t& cfg, const uint8_t* code,
+                           uint32_t code_all, const uint8_t* map, const uint16_t* mtu, uint32_t mtu_all, uint8_t* dst,
+                           uint64_t dst_len, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len,
+                           const pkt_chain_t* out_chain = nullptr, uint32_t* src_index = nullptr, uint8_t* status = nullptr,
+                           uint32_t* out_index = nullptr, const uint8_t* select = nullptr, uint32_t which_ip = 0,
+                           uint32_t flags = 0, uint64_t* hits = nullptr, hipStream_t s = nullptr) {
+        FragTotals t;
+        const int rc = pkt_icmp_err_batch(ctx_, &b, &chain, which_ip, flags, &cfg, code, code_all, map, mtu, mtu_all, select,
+                                          status, out_index, dst, dst_len, out_cap, out_off, out_len, src_index, out_chain, hits,
+                                          &t.bytes, &t.n_out, s);
+        if (rc == PKT_ERR_INVALID_ARG && (t.n_out || t.bytes)) {
+            t.fits = false;
+            return t;
+        }
+        check(rc, ctx_, "pkt_icmp_err_batch");
+        return t;
+    }
+
     // IPv4 reassembly of a batch's fragments (pkt_reasm_batch), the inverse of fragment: the fragments are grouped by
     // (src, dst, protocol, identification) and every datagram that is complete in this batch is joined into one packet
     // at the place of its last-arriving member; packets that are no fragments go through whole.  dst, out_off /

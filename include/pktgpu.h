@@ -1180,7 +1180,7 @@ const char *pkt_lpm_last_error(const pkt_lpm_t *lpm);
  * pkt_fwd_host is the same operation on HOST pointers: no ctx, no device, no handle.  Its lpm, if given, must be a
  * handle from pkt_lpm_create_host; the slab's 16-byte alignment rule is waived, as for that handle.
  * Out of scope: VLAN push or rewrite (pkt_edit_batch / pkt_set_fields); ICMP time-exceeded and fragmentation-needed
- * generation (fragmentation itself is pkt_frag_batch, below: it takes the PKT_FWD_MTU packets); ECMP; per-adjacency counters (a bincount of adj_index); NAT; IPv4 options and
+ * generation (pkt_icmp_err_batch, below, takes this call's status array; fragmentation itself is pkt_frag_batch, below: it takes the PKT_FWD_MTU packets); ECMP; per-adjacency counters (a bincount of adj_index); NAT; IPv4 options and
  * IPv6 extension headers (the walk models neither). */
 typedef struct pkt_fwd_adj {       /* 20 bytes */
     uint8_t  dmac[6];              /* written to the Ether header's bytes 0..5 */
@@ -1295,7 +1295,8 @@ int pkt_fwd_host(const pkt_fwd_adj_t *adj, uint32_t nadj, const pkt_batch_t *bat
  *    stored whole).  No lane waits for another; no global atomics but the hits adds.
  * pkt_frag_host is the same operation on HOST pointers: no ctx, no device; the slab's and dst's alignment rules hold
  * for dst, hits, out_off and mtu and are waived for the slab.
- * Out of scope: ICMP fragmentation-needed / packet-too-big generation (PKT_FRAG_DF and PKT_FRAG_IPV6 are its inputs);
+ * Out of scope: ICMP fragmentation-needed / packet-too-big generation (pkt_icmp_err_batch, below: PKT_FRAG_DF and
+ * PKT_FRAG_IPV6 are its inputs);
  * reassembly (pkt_reasm_batch, below); IPv4 options; fixing outer tunnel lengths. */
 typedef enum pkt_frag_status {
     PKT_FRAG_FITS    = 0, /* one output: the packet, whole */
@@ -1522,6 +1523,157 @@ int pkt_scan_batch(pkt_scan_t *s, const pkt_batch_t *batch, const pkt_chain_t *c
                    uint8_t *sel, uint32_t *count, uint64_t *matched, uint64_t *hits, void *stream);
 int pkt_scan_destroy(pkt_scan_t *s);
 const char *pkt_scan_last_error(const pkt_scan_t *s);
+
+/* ---- ICMP errors for the packets a router refuses ----
+ * What a router answers to the packets pkt_fwd_batch leaves at PKT_FWD_TTL / _MTU / _NO_ADJ and pkt_frag_batch at
+ * PKT_FRAG_DF / _IPV6: for every source packet that may be answered one ICMP (IPv4) or ICMPv6 (IPv6) error packet,
+ * packed into a second slab exactly as pkt_frag_batch packs its outputs, with the chain columns the following calls
+ * need.  The reference defines nothing here, so this header fixes the semantics; they follow RFC 792, RFC 1191,
+ * RFC 1122 3.2.2, RFC 1812 4.3.2 and RFC 4443 2.4.
+ *
+ * The code.  Packet i's code is c = code ? code[i] : code_all (code_all > 255 is refused), its reason r = map ?
+ * map[c] : c.  `map` is a HOST array of 256 bytes that goes along with the launch (it need not outlive the call), so
+ * pkt_fwd_batch's or pkt_frag_batch's device status array is `code` as it is, with no pass in between.  A reason
+ * (pkt_icmp_reason_t) gives a (type, code) pair per IP version:
+ *    reason          IPv4      IPv6
+ *    TIME_EXCEEDED   11, 0     3, 0
+ *    TOO_BIG          3, 4     2, 0     the next-hop mtu m = mtu ? mtu[i] : mtu_all goes into bytes 6..7 of the ICMP
+ *    NET_UNREACH      3, 0     1, 0     header under IPv4 (RFC 1191) and bytes 4..7 under IPv6
+ *    HOST_UNREACH     3, 1     1, 3
+ *    PROHIBITED       3, 13    1, 1
+ *    PORT_UNREACH     3, 3     1, 4
+ *
+ * pkt_icmp_err_batch, per source packet i: the first test that applies gives status[i].
+ *  1. select != NULL && select[i] == 0, or r == 0: PKT_ICMPE_SKIPPED.
+ *  2. r > 6: PKT_ICMPE_BAD_REASON.
+ *  3. The IP entry is found exactly as in pkt_frag_batch step 2 (which_ip, PKT_FLOW_LAST included, over min(n_hdrs,
+ *     PKT_MAX_HDRS) entries).  No such entry: PKT_ICMPE_NO_IP.  Its H = 20 / 40 bytes not inside the packet's length
+ *     (under the pkt_batch_t clamp rules): PKT_ICMPE_SPAN.
+ *  4. The Ether entry with the greatest index below the IP entry (pkt_fwd_batch's rule).  None: PKT_ICMPE_NO_ETHER.
+ *     eth_off + 14 > ip_off (only a forged chain gives that): PKT_ICMPE_SPAN.  P = ip_off - eth_off.
+ *  5. The cfg's source address for this IP version is all zero: PKT_ICMPE_NO_SRC.
+ *  6. IPv4: byte 0 != 0x45, or L = bytes 2..3 < 20 (IPv4 options are out of scope, as in pkt_frag_batch); IPv6:
+ *     byte 0 >> 4 != 6: PKT_ICMPE_BAD_HDR.
+ *  7. IPv4 with (bytes 6..7 & 0x1FFF) != 0, a non-first fragment (RFC 1122 3.2.2): PKT_ICMPE_FRAGMENT.  A first
+ *     fragment (MF set, offset 0) is answered.
+ *  8. The packet's source address names no single host: IPv4 with first byte 0, 127 or >= 224; IPv6 all zero or with
+ *     first byte 0xFF: PKT_ICMPE_BAD_SRC.
+ *  9. The Ether destination's byte 0 has bit 0 set, or the IPv4 destination's first byte is >= 224, or the IPv6
+ *     destination's first byte is 0xFF: PKT_ICMPE_MCAST.  The step does not apply to IPv6 with r == TOO_BIG (RFC 4443
+ *     2.4 e.3).
+ * 10. The packet is itself an ICMP error: PKT_ICMPE_ICMP_ERR.  IPv4 with protocol byte 1: the type byte at ip_off +
+ *     20 lies outside min(len, ip_off + L), or it is one of 3, 4, 5, 11, 12.  IPv6 with next header 58: the type byte
+ *     at ip_off + 40 lies outside min(len, ip_off + 40 + bytes 4..5), or it is < 128 or == 137.
+ * 11. PKT_ICMPE_SENT: one output.
+ * The output of a SENT packet, out_len = P + H + 8 + Q bytes (not padded to 60):
+ *  - bytes [0, P): the source's [eth_off, ip_off) verbatim (VLAN tags, MPLS labels and all) with the two MAC
+ *    addresses swapped: the reply leaves by the link it came in on, and pkt_fwd_batch over the output re-routes it if
+ *    the caller wants that.  Outer tunnel headers before eth_off are NOT carried: an error for a VXLAN inner packet
+ *    is a bare inner frame, for pkt_edit_batch to encapsulate;
+ *  - IPv4 header: 45 tos, total length 28 + Q, identification (ident + q) & 0xFFFF with q the output's index, bytes
+ *    6..7 zero, ttl, protocol 1, the RFC 1071 header checksum (the correct fold, not Packet::ipv4_checksum's), src4,
+ *    the source packet's source address;
+ *  - IPv6 header: version 6, traffic class tos, flow label 0, payload length 8 + Q, next header 58, hop limit ttl,
+ *    src6, the source packet's source address;
+ *  - ICMP header, 8 bytes: type, code, checksum, and four bytes that are zero but for TOO_BIG's mtu;
+ *  - the quote: the source bytes [ip_off, ip_off + Q) verbatim (pkt_fwd_batch does not write a packet it refuses, so
+ *    the ttl is as received).  Q = min(avail, max - H - 8), max = max4 / max6; avail = min(L, len - ip_off) under
+ *    IPv4 and min(40 + bytes 4..5, len - ip_off) under IPv6: Ethernet padding is never quoted, and a truncated
+ *    capture record is quoted as far as it goes;
+ *  - the ICMP checksum: RFC 1071 over the ICMP message, under IPv6 with the pseudo-header (src, dst, the 32-bit
+ *    length 8 + Q, next header 58); a computed 0 is stored as 0xFFFF under IPv6 and as 0 under IPv4, exactly the
+ *    encodings pkt_l4_checksum_batch calls PKT_L4_OK.
+ * Outputs are in source order, exact and the same from run to run.  Per source packet: status[i] and out_index[i],
+ * the packet's output or PKT_ICMPE_NONE.  Per output q: out_off, out_len, src_index and out_chain; dst, out_off, the
+ * layout rule (out_off[q + 1] = out_off[q] + round_up(out_len[q], 16), the rounded tail zeros), the empty tail
+ * [*n_out, out_cap) (out_off 0, out_len 0, src_index PKT_ICMPE_NONE, out_chain->n_hdrs 0), PKT_ICMPE_NO_WRITE (the
+ * sizing pass: only status, out_index, hits and the totals), the overflow return with both totals set and decided on
+ * the device, and _async / _result with one call in flight per ctx are pkt_frag_batch's, word for word.  status,
+ * out_index, src_index, hits, out_chain and each of its columns may be NULL.
+ * out_chain: rows 0..(e_ip - e_eth) are the source's rows e_eth..e_ip (the Ether and the IP entry's indices) with
+ * hdr_off - eth_off, then one row (PKT_HDR_ICMP, P + H); n_hdrs = min(e_ip - e_eth + 2, PKT_MAX_HDRS), and the ICMP row
+ * is written only if its index is below PKT_MAX_HDRS.  pkt_l4_checksum_batch, pkt_flow_key_batch,
+ * pkt_lpm_lookup_batch, pkt_fwd_batch (which routes the replies), pkt_dispatch_batch and pkt_pcap_write take the
+ * result with no second parse.
+ * hits: device uint64_t[PKT_ICMPE_STATUS_COUNT], 8-byte aligned, ADDED to; exact, every call adds exactly n.
+ *  - PKT_ERR_INVALID_ARG before any launch, with a text starting "pkt_icmp_err" in pkt_ctx_last_error:
+ *    pkt_frag_batch's batch, slab, chain, which_ip, flag, alignment (dst 16, hits 8, out_off 8, mtu 2) and capacity
+ *    rules; a NULL cfg; a cfg with both addresses zero; max4 not 0 and below 56, max6 not 0 and below 96; code_all >
+ *    255; mtu_all > 65535; a second call on the ctx before pkt_icmp_err_result.  n == 0 succeeds with both totals 0
+ *    and writes the empty tail.
+ *  - Scratch lives in the ctx and grows on demand.
+ *  - On the device, three launches: a decision kernel (a lane owns a source packet: the chain, the header bytes the
+ *    tests need by the aligned 16-byte chunks that hold them, a 32-byte plan; per tile of 256 the outputs and rounded
+ *    bytes; per-status counts merged per block in LDS), a one-block scan that also decides the overflow, and a build
+ *    kernel (a wave walks the 16-byte chunks of its 64 sources' outputs together; each chunk is built in registers
+ *    from the swapped prefix, the header words and the two aligned source chunks that hold its quote bytes, and
+ *    stored whole; the quote's 16-bit words are summed chunk by chunk into the output's LDS word, and the chunks that
+ *    hold the ICMP checksum are stored once the wave's sums are complete).  No lane waits for another; no global
+ *    atomics but the hits adds.
+ * pkt_icmp_err_host is the same operation on HOST pointers: no ctx, no device; the alignment rules hold for dst,
+ * hits, out_off and mtu and are waived for the slab.
+ * Out of scope: rate limiting (RFC 1812 4.3.2.8: the caller's `select`); per-interface source addresses; redirects,
+ * parameter problem, echo replies; IPv4 options and IPv6 extension headers; directed-broadcast destinations. */
+typedef struct pkt_icmp_cfg {      /* 28 bytes */
+    uint8_t  src4[4];              /* the router's IPv4 address, wire bytes; all zero = no IPv4 errors are sent */
+    uint8_t  src6[16];             /* the same for IPv6 */
+    uint16_t max4;                 /* greatest IPv4 datagram built (IP header on), 0 = 576 (RFC 1812 4.3.2.3); else 56..65535 */
+    uint16_t max6;                 /* greatest IPv6 packet built, 0 = 1280 (RFC 4443 2.4 c); else 96..65535 */
+    uint16_t ident;                /* IPv4 identification of output q is (ident + q) & 0xFFFF */
+    uint8_t  ttl;                  /* ttl / hop limit of the outputs, 0 = 64 */
+    uint8_t  tos;                  /* tos / traffic class of the outputs */
+} pkt_icmp_cfg_t;
+typedef enum pkt_icmp_reason {
+    PKT_ICMP_R_NONE          = 0,  /* no answer: PKT_ICMPE_SKIPPED */
+    PKT_ICMP_R_TIME_EXCEEDED = 1,
+    PKT_ICMP_R_TOO_BIG       = 2,
+    PKT_ICMP_R_NET_UNREACH   = 3,
+    PKT_ICMP_R_HOST_UNREACH  = 4,
+    PKT_ICMP_R_PROHIBITED    = 5,
+    PKT_ICMP_R_PORT_UNREACH  = 6
+} pkt_icmp_reason_t;
+typedef enum pkt_icmpe_status {
+    PKT_ICMPE_SENT       = 0,  /* one output */
+    PKT_ICMPE_SKIPPED    = 1,  /* select[i] == 0, or reason 0 */
+    PKT_ICMPE_BAD_REASON = 2,  /* reason above 6 */
+    PKT_ICMPE_NO_IP      = 3,  /* the chain has no such IPv4 / IPv6 entry */
+    PKT_ICMPE_SPAN       = 4,  /* the IP entry's bytes are not inside the packet, or the Ether entry runs into it */
+    PKT_ICMPE_NO_ETHER   = 5,  /* no Ether entry before the IP entry */
+    PKT_ICMPE_NO_SRC     = 6,  /* the cfg has no source address for this IP version */
+    PKT_ICMPE_BAD_HDR    = 7,  /* IPv4 byte 0 != 0x45 or total length < 20; IPv6 version != 6 */
+    PKT_ICMPE_FRAGMENT   = 8,  /* a non-first IPv4 fragment */
+    PKT_ICMPE_BAD_SRC    = 9,  /* the source address names no single host */
+    PKT_ICMPE_MCAST      = 10, /* sent to a link-layer or IP multicast / broadcast destination */
+    PKT_ICMPE_ICMP_ERR   = 11  /* the packet is itself an ICMP error */
+} pkt_icmpe_status_t;
+#define PKT_ICMPE_STATUS_COUNT 12
+#define PKT_ICMPE_NO_WRITE 1u          /* flags: decide and total everything, store no packet byte and no per-output array */
+#define PKT_ICMPE_NONE     0xFFFFFFFFu /* out_index[i] / src_index[q] when there is none */
+size_t pkt_sizeof_icmp_cfg(void);
+int pkt_icmp_err_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                       uint32_t flags, const pkt_icmp_cfg_t *cfg, const uint8_t *code, uint32_t code_all,
+                       const uint8_t *map, const uint16_t *mtu, uint32_t mtu_all, const uint8_t *select,
+                       uint8_t *status, uint32_t *out_index,
+                       uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                       uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                       const pkt_chain_t *out_chain,
+                       uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out, void *stream);
+int pkt_icmp_err_batch_async(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                             uint32_t flags, const pkt_icmp_cfg_t *cfg, const uint8_t *code, uint32_t code_all,
+                             const uint8_t *map, const uint16_t *mtu, uint32_t mtu_all, const uint8_t *select,
+                             uint8_t *status, uint32_t *out_index,
+                             uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                             uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                             const pkt_chain_t *out_chain, uint64_t *hits, void *stream);
+int pkt_icmp_err_result(pkt_ctx_t *ctx, uint64_t *bytes_out_total, uint64_t *n_out);
+int pkt_icmp_err_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                      uint32_t flags, const pkt_icmp_cfg_t *cfg, const uint8_t *code, uint32_t code_all,
+                      const uint8_t *map, const uint16_t *mtu, uint32_t mtu_all, const uint8_t *select,
+                      uint8_t *status, uint32_t *out_index,
+                      uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                      uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                      const pkt_chain_t *out_chain,
+                      uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
 
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);

@@ -1,7 +1,7 @@
 // pktgpu_ctx.hpp — the pkt_ctx behind the C ABI's opaque handle and the internal entry points the sources
 // share: the kernel sources (pktgpu.hip: parse; pktgpu_rewrite.hip: getters, to_vec, setters; pktgpu_pcap.hip /
 // pktgpu_pcapw.hip: pcap indexer / writer; pktgpu_compare.hip, pktgpu_edit.hip, pktgpu_l4csum.hip, pktgpu_flow.hip, pktgpu_match.hip,
-// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_reasm.hip, pktgpu_scan.hip, pktgpu_gen.hip,
+// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_reasm.hip, pktgpu_scan.hip, pktgpu_icmp.hip, pktgpu_gen.hip,
 // pktgpu_gather.hip) and the
 // host-only ones (pktgpu_ctx.cpp: lifecycle and knobs; pktgpu_hostpath.cpp: host-memory paths; pktgpu_mgpu.cpp).
 #pragma once
@@ -106,6 +106,14 @@ struct ReasmScratch : QueuedResult {
     uint64_t bytes = 0;
 };
 
+// Scratch of pkt_icmp_err_batch (pktgpu_icmp.hip), grown on demand: the totals' device words, the tile sums and the
+// per-packet plans.  Its result words: [total rounded bytes, outputs, nonzero = they did not fit]; pending: a call
+// queued by pkt_icmp_err_batch_async.
+struct IcmpScratch : QueuedResult {
+    void* buf = nullptr;
+    uint64_t bytes = 0;
+};
+
 // Scratch of pkt_compare_batch (pktgpu_compare.hip): 256 slots of four device words the blocks add
 // their counts to (equal, len, bytes; the lowest bad index as the maximum of its complement), all zero
 // between calls, and the pinned words their sums are copied to: [n_equal, n_len, n_bytes, first_bad
@@ -155,6 +163,7 @@ struct pkt_ctx {
     PcapWriteScratch pw;
     FragScratch fr;
     ReasmScratch rs;
+    IcmpScratch ic;
     CompareScratch cmp;
     MaxScratch mx;
     uint32_t window = 0;  // 0 = auto

@@ -16,6 +16,7 @@
 #include "pktgpu_frag.hpp"
 #include "pktgpu_reasm.hpp"
 #include "pktgpu_scan.hpp"
+#include "pktgpu_icmp.hpp"
 
 namespace {
 
@@ -1376,6 +1377,121 @@ int pkt_reasm_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t whic
     } catch (const std::bad_alloc&) {  // the twin keeps O(n) host memory
         return PKT_ERR_UNSUPPORTED;
     }
+}
+
+// ---- pkt_icmp_err_batch on host pointers (the CPU twin of pktgpu_icmp.hip): two sequential passes over the packets
+// with the find step, the decision, the header builders and the refusals of pktgpu_icmp.hpp, which the kernels share.
+// The first pass decides and totals; the second, when the outputs fit, writes them a byte at a time and sums the quote
+// with the plain RFC 1071 loop.
+namespace {
+
+IcmpPlan icmp_plan_host(const BatchSrc& src, const pkt_chain_t* chain, uint64_t n, uint64_t i, uint32_t which_ip,
+                        const IcmpCfg& cfg, const uint8_t* code, uint32_t code_all, const uint16_t* mtu, uint32_t mtu_all,
+                        const uint8_t* select) {
+    const uint64_t off = pkt_off(src, i);
+    const uint32_t len = pkt_len(src, i, off);
+    IcmpPlan p{};
+    const uint32_t c = code ? code[i] : code_all;
+    const uint32_t r = cfg.has_map ? cfg.map[c & 0xFFu] : c;
+    p.st = icmp_reason_status(select ? select[i] : 1u, r);
+    if (p.st != PKT_ICMPE_SENT) return p;
+    uint32_t nh = chain->n_hdrs[i];
+    nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+    IcmpFind f;
+    for (uint32_t j = 0; j < nh; j++) icmp_find_step(f, which_ip, j, chain->hdr_type[j * n + i], chain->hdr_off[j * n + i]);
+    p.st = icmp_find_status(f, len);
+    if (p.st != PKT_ICMPE_SENT) return p;
+    const uint8_t* s = src.slab + off;
+    const uint32_t H = f.ipt == PKT_HDR_IPV4 ? 20u : 40u;
+    uint32_t h[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t k = 0; k < 28u && k < H; k++) h[k >> 2] |= (uint32_t)s[f.ipo + k] << (8u * (k & 3u));
+    const uint32_t tb = f.ipo + H < len ? s[f.ipo + H] : 0u;
+    icmp_decide(p, f, len, r, h, tb, s[f.eth], mtu ? mtu[i] : mtu_all, cfg);
+    return p;
+}
+
+}  // namespace
+
+size_t pkt_sizeof_icmp_cfg(void) { return sizeof(pkt_icmp_cfg_t); }
+
+int pkt_icmp_err_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
+                      const pkt_icmp_cfg_t* cfg, const uint8_t* code, uint32_t code_all, const uint8_t* map,
+                      const uint16_t* mtu, uint32_t mtu_all, const uint8_t* select, uint8_t* status, uint32_t* out_index,
+                      uint8_t* dst, uint64_t dst_len, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len,
+                      uint32_t* src_index, const pkt_chain_t* out_chain, uint64_t* hits, uint64_t* bytes_out_total,
+                      uint64_t* n_out) {
+    if (bytes_out_total) *bytes_out_total = 0;
+    if (n_out) *n_out = 0;
+    if (icmp_call_error(b, chain, which_ip, flags, cfg, code_all, mtu, mtu_all, dst, out_cap, out_off, out_len, hits, false))
+        return PKT_ERR_INVALID_ARG;
+    const uint64_t n = b->n;
+    const bool write = !(flags & PKT_ICMPE_NO_WRITE);
+    const BatchSrc src = batch_src(b);
+    const IcmpCfg cf = icmp_cfg(*cfg, map);
+    uint64_t q = 0, bytes = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const IcmpPlan p = icmp_plan_host(src, chain, n, i, which_ip, cf, code, code_all, mtu, mtu_all, select);
+        const bool sent = p.st == PKT_ICMPE_SENT;
+        if (status) status[i] = (uint8_t)p.st;
+        if (out_index) out_index[i] = sent ? (uint32_t)q : PKT_ICMPE_NONE;
+        if (hits) hits[p.st] += 1;
+        if (sent) {
+            q += 1;
+            bytes += frag_round16(icmp_out_len(p));
+        }
+    }
+    if (bytes_out_total) *bytes_out_total = bytes;
+    if (n_out) *n_out = q;
+    if (!write) return PKT_SUCCESS;
+    if (frag_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
+    uint8_t* oc_nh = out_chain ? const_cast<uint8_t*>(out_chain->n_hdrs) : nullptr;
+    uint8_t* oc_ty = out_chain ? const_cast<uint8_t*>(out_chain->hdr_type) : nullptr;
+    uint16_t* oc_of = out_chain ? const_cast<uint16_t*>(out_chain->hdr_off) : nullptr;
+    q = 0;
+    uint64_t pos = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const IcmpPlan p = icmp_plan_host(src, chain, n, i, which_ip, cf, code, code_all, mtu, mtu_all, select);
+        if (p.st != PKT_ICMPE_SENT) continue;
+        const uint8_t* s = src.slab + pkt_off(src, i);
+        const uint32_t P = p.ipo - p.eth, H = icmp_hlen(p), ol = icmp_out_len(p);
+        uint8_t* d = dst + pos;
+        memcpy(d, s + p.eth, P);
+        memcpy(d, s + p.eth + 6, 6);
+        memcpy(d + 6, s + p.eth, 6);
+        uint32_t w[12];
+        const uint32_t part = icmp_headers(p, q, cf, w);
+        for (uint32_t k = 0; k < H + 8u; k++) d[P + k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
+        const uint8_t* quote = s + p.ipo;
+        memcpy(d + P + H + 8u, quote, p.q);
+        uint32_t qs = 0;
+        for (uint32_t k = 0; k < p.q; k++) qs += k & 1u ? quote[k] : (uint32_t)quote[k] << 8;
+        const uint32_t c = icmp_csum(p, part, qs);
+        d[P + H + 2u] = (uint8_t)(c >> 8);
+        d[P + H + 3u] = (uint8_t)c;
+        memset(d + ol, 0, frag_round16(ol) - ol);
+        out_off[q] = pos;
+        out_len[q] = ol;
+        if (src_index) src_index[q] = (uint32_t)i;
+        const uint32_t rows = p.e_ip - p.e_eth + 1u;
+        if (oc_nh) oc_nh[q] = (uint8_t)(rows + 1u > PKT_MAX_HDRS ? PKT_MAX_HDRS : rows + 1u);
+        for (uint32_t r = 0; r < rows; r++) {
+            if (oc_ty) oc_ty[r * out_cap + q] = chain->hdr_type[(p.e_eth + r) * n + i];
+            if (oc_of) oc_of[r * out_cap + q] = (uint16_t)(chain->hdr_off[(p.e_eth + r) * n + i] - p.eth);
+        }
+        if (rows < PKT_MAX_HDRS) {
+            if (oc_ty) oc_ty[rows * out_cap + q] = PKT_HDR_ICMP;
+            if (oc_of) oc_of[rows * out_cap + q] = (uint16_t)(P + H);
+        }
+        pos += frag_round16(ol);
+        q++;
+    }
+    for (; q < out_cap; q++) {
+        out_off[q] = 0;
+        out_len[q] = 0;
+        if (src_index) src_index[q] = PKT_ICMPE_NONE;
+        if (oc_nh) oc_nh[q] = 0;
+    }
+    return PKT_SUCCESS;
 }
 
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,

@@ -782,6 +782,26 @@ class Parser:
         return _reassemble(self, batch, chain, select, which_ip, only_joined, plan_only, out_cap, dst_bytes, hits, host,
                            stream)
 
+    def icmp_errors(self, batch, chain, reason=None, fwd_status=None, frag_status=None, mtu=0, src4=None, src6=None,
+                    ttl=64, tos=0, max4=576, max6=1280, ident=0, select=None, which_ip=0, plan_only=False, out_cap=None,
+                    dst_bytes=None, hits=None, host=False, stream=None):
+        """pkt_icmp_err_batch: one ICMP (IPv4) or ICMPv6 (IPv6) error packet for every packet of the batch that was
+        refused and may be answered, packed at 16-byte-aligned offsets of a new slab -> IcmpErrResult.  Exactly one of
+        `reason` (an int for the batch or a uint8 [n] array of schema.ICMP_R_*), `fwd_status` (Forwarder.run's status
+        array, read through schema.ICMP_MAP_FWD: TTL -> time exceeded, MTU -> too big, NO_ADJ -> net unreachable) and
+        `frag_status` (fragment's, through schema.ICMP_MAP_FRAG: DF and IPV6 -> too big) is given.  `mtu`: the next
+        hop's mtu a too-big error reports, one number or a uint16 [n] array.  src4 / src6: the router's addresses
+        ("192.0.2.1", "2001:db8::1" or 4 / 16 bytes); an IP version without one is not answered.  ttl, tos, ident and
+        max4 / max6 (the greatest datagram built) fill the new headers.  `select`, `which_ip`, plan_only, out_cap /
+        dst_bytes, hits (uint64 [12]) and host=True are as fragment takes them.  The replies leave by the link the
+        packets came in on (MACs swapped); to route them instead:
+
+            r = fwd.run(batch, chain, lpm=lpm)
+            e = p.icmp_errors(batch, chain, fwd_status=r["status"], mtu=adj_mtu[r["adj_index"]], src4="192.0.2.1")
+            fwd.run(e.batch(), e.out_chain, lpm=lpm)"""
+        return _icmp_errors(self, batch, chain, reason, fwd_status, frag_status, mtu, src4, src6, ttl, tos, max4, max6,
+                            ident, select, which_ip, plan_only, out_cap, dst_bytes, hits, host, stream)
+
     def scanner(self, patterns, nocase=False, groups=None, actions=None, default=0, host=False):
         """pkt_scan_create: compile a set of byte strings (bytes or str, 1..64 bytes each, at most 8192 of them and
         131072 bytes in all) on this parser's device -> Scanner.  `nocase`: one bool for the set or one per pattern
@@ -1914,6 +1934,142 @@ def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only
                out_chain=dict(n_hdrs=empty(cap, np.uint8), hdr_type=empty((schema.MAX_HDRS, cap), np.uint8),
                               hdr_off=empty((schema.MAX_HDRS, cap), np.uint16)))
     done(call(flags, out, True), "pkt_frag_batch")
+    out.pop("cap")
+    res.__dict__.update(out, n_out=cnt.value, bytes_out=tot.value)
+    return res
+
+
+(ICMPE_SENT, ICMPE_SKIPPED, ICMPE_BAD_REASON, ICMPE_NO_IP, ICMPE_SPAN, ICMPE_NO_ETHER, ICMPE_NO_SRC, ICMPE_BAD_HDR,
+ ICMPE_FRAGMENT, ICMPE_BAD_SRC, ICMPE_MCAST, ICMPE_ICMP_ERR) = range(12)
+ICMPE_NONE, ICMPE_NO_WRITE = schema.ICMPE_NONE, schema.ICMPE_NO_WRITE
+
+
+class IcmpErrResult:
+    """What Parser.icmp_errors gives.  Per source packet: status (uint8: pktgpu.ICMPE_SENT / _SKIPPED / _BAD_REASON /
+    _NO_IP / _SPAN / _NO_ETHER / _NO_SRC / _BAD_HDR / _FRAGMENT / _BAD_SRC / _MCAST / _ICMP_ERR) and out_index (uint32:
+    the packet's output, ICMPE_NONE where there is none).  The totals: n_out, bytes_out.  Unless plan_only, per output
+    (arrays of out_cap entries, empty past n_out): slab, offsets, lens, src_index and out_chain ({"n_hdrs",
+    "hdr_type", "hdr_off"}, slot-major over out_cap); batch() is the output as the batch dict the other calls take.
+    hits: the per-status counters, if asked for."""
+
+    def __init__(self, **kw):
+        self.slab = self.offsets = self.lens = self.src_index = self.out_chain = self.hits = None
+        self.__dict__.update(kw)
+
+    def batch(self):
+        return dict(slab=self.slab, offsets=self.offsets, lens=self.lens)
+
+
+def _icmp_addr(a, size, what):
+    """An address given as a string or as bytes -> `size` wire bytes (None: all zero, no errors of that version)."""
+    import socket
+    if a is None:
+        return bytes(size)
+    if isinstance(a, str):
+        a = socket.inet_pton(socket.AF_INET if size == 4 else socket.AF_INET6, a)
+    a = bytes(a)
+    if len(a) != size:
+        raise ValueError(f"icmp_errors: {what} is {size} bytes or an address string")
+    return a
+
+
+def _icmp_errors(parser, batch, chain, reason, fwd_status, frag_status, mtu, src4, src6, ttl, tos, max4, max6, ident,
+                 select, which_ip, plan_only, out_cap, dst_bytes, hits, host, stream):
+    from . import _lib
+    L = _lib.load()
+    if sum(x is not None for x in (reason, fwd_status, frag_status)) != 1:
+        raise ValueError("icmp_errors: exactly one of reason, fwd_status and frag_status")
+    code, cmap = reason, None
+    if fwd_status is not None:
+        code, cmap = fwd_status, schema.ICMP_MAP_FWD
+    elif frag_status is not None:
+        code, cmap = frag_status, schema.ICMP_MAP_FRAG
+    if hasattr(batch, "batch") and callable(batch.batch):
+        batch = batch.batch()
+    if isinstance(batch, (tuple, list)):
+        batch = dict(zip(("slab", "offsets", "lens"), batch))
+    g = lambda k: batch.get(k)  # noqa: E731
+    nc = schema.ICMPE_STATUS_COUNT
+    scalar = lambda v: isinstance(v, (int, np.integer))  # noqa: E731
+    if host:
+        b, keep = _host_batch(_lib, batch)
+        cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                np.ascontiguousarray(chain["hdr_off"], np.uint16))
+        ch = _lib.PktChain(*[c.ctypes.data for c in cols])
+        select = None if select is None else np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+        empty = lambda k, dt: np.zeros(k, dt)  # noqa: E731
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
+        if not scalar(mtu):
+            mtu = np.ascontiguousarray(mtu, np.uint16)
+        if not scalar(code):
+            code = np.ascontiguousarray(code, np.uint8)
+    else:
+        torch = _torch()
+        b = parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
+        ch = parser._chain(chain)
+        dev = parser.torch_device
+        assert select is None or (select.is_cuda and select.dtype == torch.uint8 and select.is_contiguous()
+                                  and select.numel() >= b.n)
+        empty = lambda k, dt: torch.zeros(k, dtype=_tdtype(dt), device=dev)  # noqa: E731
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
+        if not scalar(mtu):
+            assert mtu.is_cuda and mtu.dtype == torch.uint16 and mtu.is_contiguous() and mtu.numel() >= b.n
+        if not scalar(code):
+            assert code.is_cuda and code.dtype == torch.uint8 and code.is_contiguous() and code.numel() >= b.n
+    if hits is True:
+        hits = empty(nc, np.uint64)
+    if hits is not None and hits is not False:
+        assert ok(hits), f"icmp_errors: hits is a contiguous uint64 [{nc}] array"
+    else:
+        hits = None
+    cfg = _lib.PktIcmpCfg()
+    cfg.src4[:] = _icmp_addr(src4, 4, "src4")
+    cfg.src6[:] = _icmp_addr(src6, 16, "src6")
+    cfg.max4, cfg.max6, cfg.ident, cfg.ttl, cfg.tos = int(max4), int(max6), int(ident) & 0xFFFF, int(ttl), int(tos)
+    n = b.n
+    res = IcmpErrResult(status=empty(n, np.uint8), out_index=empty(n, np.uint32), hits=hits)
+    tot, cnt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def call(fl, out, with_hits):
+        dst, cap = out.get("slab"), out.get("cap", 0)
+        oc = None
+        if out:
+            oc = _lib.PktChain(*[ptr(out["out_chain"][k]) for k in ("n_hdrs", "hdr_type", "hdr_off")])
+        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), fl, ctypes.byref(cfg),
+                None if scalar(code) else ptr(code), int(code) if scalar(code) else 0,
+                None if cmap is None else cmap.ctypes.data, None if scalar(mtu) else ptr(mtu),
+                int(mtu) if scalar(mtu) else 0, ptr(select), ptr(res.status), ptr(res.out_index),
+                dst.ctypes.data if host and dst is not None else dst.data_ptr() if dst is not None else None,
+                0 if dst is None else int(dst.size if host else dst.numel()), cap, ptr(out.get("offsets")), ptr(out.get("lens")),
+                ptr(out.get("src_index")), ctypes.byref(oc) if oc is not None else None,
+                ptr(hits) if with_hits else None, ctypes.byref(tot), ctypes.byref(cnt))
+        if host:
+            return L.pkt_icmp_err_host(*args)
+        return L.pkt_icmp_err_batch(parser._ctx, *args, parser._stream(stream))
+
+    def done(rc, what):
+        if rc == 0:
+            return
+        if host:
+            raise ValueError(f"pkt_icmp_err_host failed ({rc}); it needs {cnt.value} outputs and {tot.value} bytes")
+        parser._check(rc, what)
+
+    sized = out_cap is not None and dst_bytes is not None
+    if plan_only or not sized:
+        done(call(schema.ICMPE_NO_WRITE, {}, plan_only), "pkt_icmp_err_batch")
+        if plan_only:
+            res.n_out, res.bytes_out = cnt.value, tot.value
+            return res
+        out_cap = cnt.value if out_cap is None else out_cap
+        dst_bytes = tot.value if dst_bytes is None else dst_bytes
+    cap = max(1, int(out_cap))
+    out = dict(slab=empty(max(16, int(dst_bytes)), np.uint8), cap=cap, offsets=empty(cap, np.uint64),
+               lens=empty(cap, np.uint32), src_index=empty(cap, np.uint32),
+               out_chain=dict(n_hdrs=empty(cap, np.uint8), hdr_type=empty((schema.MAX_HDRS, cap), np.uint8),
+                              hdr_off=empty((schema.MAX_HDRS, cap), np.uint16)))
+    done(call(0, out, True), "pkt_icmp_err_batch")
     out.pop("cap")
     res.__dict__.update(out, n_out=cnt.value, bytes_out=tot.value)
     return res

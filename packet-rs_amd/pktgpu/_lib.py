@@ -98,6 +98,11 @@ class PktLpmInfo(ctypes.Structure):
                                                "bytes")]
 
 
+class PktIcmpCfg(ctypes.Structure):
+    _fields_ = [("src4", ctypes.c_uint8 * 4), ("src6", ctypes.c_uint8 * 16), ("max4", ctypes.c_uint16),
+                ("max6", ctypes.c_uint16), ("ident", ctypes.c_uint16), ("ttl", ctypes.c_uint8), ("tos", ctypes.c_uint8)]
+
+
 class PktFwdAdj(ctypes.Structure):
     _fields_ = [("dmac", ctypes.c_uint8 * 6), ("smac", ctypes.c_uint8 * 6), ("port", ctypes.c_uint32),
                 ("mtu", ctypes.c_uint16), ("action", ctypes.c_uint8), ("zero", ctypes.c_uint8)]
@@ -290,6 +295,22 @@ SIGNATURES = {
                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pkt_scan_destroy": (ctypes.c_int, [_P]),
     "pkt_scan_last_error": (ctypes.c_char_p, [_P]),
+    "pkt_sizeof_icmp_cfg": (ctypes.c_size_t, []),
+    "pkt_icmp_err_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                          ctypes.c_uint32, ctypes.POINTER(PktIcmpCfg), _P, ctypes.c_uint32, _P, _P,
+                                          ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
+                                          ctypes.POINTER(PktChain), _P, ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(ctypes.c_uint64), _P]),
+    "pkt_icmp_err_batch_async": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                                ctypes.c_uint32, ctypes.POINTER(PktIcmpCfg), _P, ctypes.c_uint32, _P, _P,
+                                                ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P,
+                                                _P, ctypes.POINTER(PktChain), _P, _P]),
+    "pkt_icmp_err_result": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_icmp_err_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.POINTER(PktIcmpCfg), _P, ctypes.c_uint32, _P, _P,
+                                         ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
+                                         ctypes.POINTER(PktChain), _P, ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.POINTER(ctypes.c_uint64)]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),

@@ -88,6 +88,35 @@ SCAN_MISS, SCAN_HIT, SCAN_SKIPPED, SCAN_NO_CHAIN, SCAN_SPAN = range(5)
 SCAN_STATUS = ["MISS", "HIT", "SKIPPED", "NO_CHAIN", "SPAN"]
 SCAN_PLACE_GLOBAL, SCAN_PLACE_LDS = range(2)
 
+# pkt_icmp_err_* (ICMP errors for the packets a router refuses): reasons, statuses, the two default maps
+(ICMP_R_NONE, ICMP_R_TIME_EXCEEDED, ICMP_R_TOO_BIG, ICMP_R_NET_UNREACH, ICMP_R_HOST_UNREACH, ICMP_R_PROHIBITED,
+ ICMP_R_PORT_UNREACH) = range(7)
+ICMP_REASON = ["NONE", "TIME_EXCEEDED", "TOO_BIG", "NET_UNREACH", "HOST_UNREACH", "PROHIBITED", "PORT_UNREACH"]
+# reason -> ((type, code) under IPv4, (type, code) under IPv6)
+ICMP_TYPE_CODE = {ICMP_R_TIME_EXCEEDED: ((11, 0), (3, 0)), ICMP_R_TOO_BIG: ((3, 4), (2, 0)),
+                  ICMP_R_NET_UNREACH: ((3, 0), (1, 0)), ICMP_R_HOST_UNREACH: ((3, 1), (1, 3)),
+                  ICMP_R_PROHIBITED: ((3, 13), (1, 1)), ICMP_R_PORT_UNREACH: ((3, 3), (1, 4))}
+(ICMPE_SENT, ICMPE_SKIPPED, ICMPE_BAD_REASON, ICMPE_NO_IP, ICMPE_SPAN, ICMPE_NO_ETHER, ICMPE_NO_SRC, ICMPE_BAD_HDR,
+ ICMPE_FRAGMENT, ICMPE_BAD_SRC, ICMPE_MCAST, ICMPE_ICMP_ERR) = range(12)
+ICMPE_STATUS = ["SENT", "SKIPPED", "BAD_REASON", "NO_IP", "SPAN", "NO_ETHER", "NO_SRC", "BAD_HDR", "FRAGMENT", "BAD_SRC",
+                "MCAST", "ICMP_ERR"]
+ICMPE_STATUS_COUNT = 12
+ICMPE_NO_WRITE = 1        # flags: decide and total everything, store no packet byte and no per-output array
+ICMPE_NONE = 0xFFFFFFFF   # out_index[i] / src_index[q] when there is none
+
+
+def _icmp_map(pairs):
+    m = np.zeros(256, np.uint8)
+    for k, v in pairs.items():
+        m[k] = v
+    m.setflags(write=False)
+    return m
+
+
+# code -> reason for Forwarder.run's status (DROP is a silent discard) and for fragment's
+ICMP_MAP_FWD = _icmp_map({FWD_TTL: ICMP_R_TIME_EXCEEDED, FWD_MTU: ICMP_R_TOO_BIG, FWD_NO_ADJ: ICMP_R_NET_UNREACH})
+ICMP_MAP_FRAG = _icmp_map({FRAG_DF: ICMP_R_TOO_BIG, FRAG_IPV6: ICMP_R_TOO_BIG})
+
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
                            ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])

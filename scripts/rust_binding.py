@@ -23,13 +23,14 @@ C_SCALARS = {"uint8_t": "u8", "uint16_t": "u16", "uint32_t": "u32", "uint64_t": 
              "pkt_match_term_t": "PktMatchTerm", "pkt_match_rule_t": "PktMatchRule", "pkt_match_t": "PktMatch",
              "pkt_dispatch_t": "PktDispatch", "pkt_lpm_route_t": "PktLpmRoute", "pkt_lpm_info_t": "PktLpmInfo",
              "pkt_lpm_t": "PktLpm", "pkt_fwd_adj_t": "PktFwdAdj", "pkt_fwd_t": "PktFwd",
-             "pkt_scan_pattern_t": "PktScanPattern", "pkt_scan_info_t": "PktScanInfo", "pkt_scan_t": "PktScan"}
+             "pkt_scan_pattern_t": "PktScanPattern", "pkt_scan_info_t": "PktScanInfo", "pkt_scan_t": "PktScan",
+             "pkt_icmp_cfg_t": "PktIcmpCfg"}
 STRUCTS = {"pkt_batch": "PktBatch", "pkt_out": "PktOut", "pkt_field_spec": "PktFieldSpec", "pkt_chain": "PktChain",
            "pkt_gen_field": "PktGenField", "pkt_gather_piece": "PktGatherPiece", "pkt_cmp_summary": "PktCmpSummary",
            "pkt_edit_op": "PktEditOp", "pkt_flow_key": "PktFlowKey", "pkt_flow_record": "PktFlowRecord",
            "pkt_match_term": "PktMatchTerm", "pkt_match_rule": "PktMatchRule", "pkt_lpm_route": "PktLpmRoute",
            "pkt_lpm_info": "PktLpmInfo", "pkt_fwd_adj": "PktFwdAdj", "pkt_scan_pattern": "PktScanPattern",
-           "pkt_scan_info": "PktScanInfo"}
+           "pkt_scan_info": "PktScanInfo", "pkt_icmp_cfg": "PktIcmpCfg"}
 
 
 def _strip(src):
