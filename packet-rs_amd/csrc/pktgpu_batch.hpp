@@ -2,8 +2,9 @@
 //   host and device: BatchSrc (a batch's five source fields, as kernels take them) with THE offset rule
 //                    (pkt_off) and THE length clamp (pkt_len), the pkt_batch_t refusal rules, and the list of
 //                    the 22 header sizes;
-//   device only:     wave_sync, wave_incl_scan, take16, the little-endian Le128, the flattened chunk walk's
-//                    locator (flat_walk, locate) and the chain's first four rows loaded up front (chain_load).
+//   device only:     wave_sync, wave_incl_scan, block_excl_scan, take16, the little-endian Le128, the flattened
+//                    chunk walk's locator (flat_walk, locate) and the chain's first four rows loaded up front
+//                    (chain_load).
 // Every object depends on this header (HDRS in the Makefile), the parse kernels' included: keep it to what is
 // settled.
 // It needs include/pktgpu.h alone (not the parser's walk, pktgpu_device.hpp), and the host part compiles without
@@ -85,6 +86,25 @@ __device__ __forceinline__ T wave_incl_scan(T x, uint32_t lane) {
         if (lane >= d) x += y;
     }
     return x;
+}
+
+// Exclusive prefix of v over the threads of a block of WAVES waves; total = the block's sum.  (s_w: one word per wave.)
+template <uint32_t WAVES>
+__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* s_w, uint64_t& total) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint64_t x = wave_incl_scan(v, lane);
+    if (lane == 63) s_w[wv] = x;
+    __syncthreads();
+    uint64_t base = 0;
+    total = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < WAVES; k++) {
+        const uint64_t t = s_w[k];
+        base += k < wv ? t : 0;
+        total += t;
+    }
+    __syncthreads();  // s_w may be written again
+    return base + x - v;
 }
 
 // o = the 16 bytes at (aligned address of v0) + sh, sh in 0..15, of the 32 bytes v0 | v1: two rounds of

@@ -37,14 +37,7 @@ int pkt_ctx_destroy(pkt_ctx_t* ctx) {
         (void)hipHostFree(ctx->mx.host);
         (void)hipFree(ctx->pc.buf);
         (void)hipHostFree(ctx->pc.ctl);
-        (void)hipFree(ctx->pw.buf);
-        (void)hipHostFree(ctx->pw.ctl);
-        (void)hipFree(ctx->fr.buf);
-        (void)hipHostFree(ctx->fr.ctl);
-        (void)hipFree(ctx->rs.buf);
-        (void)hipHostFree(ctx->rs.ctl);
-        (void)hipFree(ctx->ic.buf);
-        (void)hipHostFree(ctx->ic.ctl);
+        for (OutScratch* o : {static_cast<OutScratch*>(&ctx->pw), &ctx->fr, &ctx->rs, &ctx->ic}) o->release();
         (void)hipFree(ctx->cmp.acc);
         (void)hipHostFree(ctx->cmp.ctl);
         for (int k = 0; k < HostPipe::kSlots; k++) {

@@ -1,13 +1,14 @@
 // pktgpu_ctx.hpp — the pkt_ctx behind the C ABI's opaque handle and the internal entry points the sources
 // share: the kernel sources (pktgpu.hip: parse; pktgpu_rewrite.hip: getters, to_vec, setters; pktgpu_pcap.hip /
 // pktgpu_pcapw.hip: pcap indexer / writer; pktgpu_compare.hip, pktgpu_edit.hip, pktgpu_l4csum.hip, pktgpu_flow.hip, pktgpu_match.hip,
-// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_reasm.hip, pktgpu_scan.hip, pktgpu_icmp.hip, pktgpu_gen.hip,
-// pktgpu_gather.hip) and the
+// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_reasm.hip, pktgpu_icmp.hip and the
+// pktgpu_outbatch.hip they share, pktgpu_scan.hip, pktgpu_gen.hip, pktgpu_gather.hip) and the
 // host-only ones (pktgpu_ctx.cpp: lifecycle and knobs; pktgpu_hostpath.cpp: host-memory paths; pktgpu_mgpu.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 #include <string>
 
 #include "../../include/pktgpu.h"
@@ -80,38 +81,36 @@ struct PcapScratch : QueuedResult {
     bool scan64 = false;          // pkt_ctx_set_pcap_scan64: 64-bit scan compositions for every file
 };
 
-// Scratch of pkt_pcap_write (pktgpu_pcapw.hip), grown on demand: the totals' device words, the tile
-// sums, the window table and the record-table columns the caller did not ask for.  Its result words:
-// [total bytes, records]; pending: a write queued by pkt_pcap_write_async.
-struct PcapWriteScratch : QueuedResult {
+// a piece of a scratch layout, rounded up so that the next one starts 16-byte aligned
+inline uint64_t round16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
+
+// Device scratch of an entry that packs outputs behind a device-side scan, grown on demand, with the entry's queued
+// result.  pkt_frag_batch, pkt_reasm_batch and pkt_icmp_err_batch (pktgpu_outbatch.hpp's contract) keep the totals'
+// device words, the tile sums and their per-packet plans, records and tables in it; their result words are [total
+// rounded bytes, outputs, nonzero = they did not fit], pending: a call queued by the entry's _async form.
+struct OutScratch : QueuedResult {
     void* buf = nullptr;
     uint64_t bytes = 0;
+    hipError_t reserve(uint64_t need) {  // at least `need` bytes; what the buffer held is not kept
+        if (need <= bytes) return hipSuccess;
+        if (buf) (void)hipFree(buf);  // (waits for the device: no earlier call still uses it)
+        buf = nullptr;
+        bytes = 0;
+        const hipError_t e = hipMalloc(&buf, need);
+        if (e == hipSuccess) bytes = need;
+        return e;
+    }
+    void release() {  // the ctx is going away
+        (void)hipFree(buf);
+        (void)hipHostFree(ctl);
+    }
+};
+
+// Scratch of pkt_pcap_write (pktgpu_pcapw.hip): the totals' device words, the tile sums, the window table and the
+// record-table columns the caller did not ask for.  Its result words: [total bytes, records]; pending: a write
+// queued by pkt_pcap_write_async.
+struct PcapWriteScratch : OutScratch {
     uint64_t dst_len = 0;         // the last queued write's capacity (total > dst_len = it did not fit)
-};
-
-// Scratch of pkt_frag_batch (pktgpu_frag.hip), grown on demand: the totals' device words, the tile sums, the
-// per-packet plans and the per-output columns the caller did not ask for.  Its result words: [total rounded
-// bytes, outputs, nonzero = they did not fit]; pending: a call queued by pkt_frag_batch_async.
-struct FragScratch : QueuedResult {
-    void* buf = nullptr;
-    uint64_t bytes = 0;
-};
-
-// Scratch of pkt_reasm_batch (pktgpu_reasm.hip), grown on demand: the totals' device words, the tile sums, the
-// per-packet records, the datagrams' words, the two open-addressed tables and src_index when the caller did not ask
-// for it.  Its result words: [total rounded bytes, outputs, nonzero = they did not fit]; pending: a call queued by
-// pkt_reasm_batch_async.
-struct ReasmScratch : QueuedResult {
-    void* buf = nullptr;
-    uint64_t bytes = 0;
-};
-
-// Scratch of pkt_icmp_err_batch (pktgpu_icmp.hip), grown on demand: the totals' device words, the tile sums and the
-// per-packet plans.  Its result words: [total rounded bytes, outputs, nonzero = they did not fit]; pending: a call
-// queued by pkt_icmp_err_batch_async.
-struct IcmpScratch : QueuedResult {
-    void* buf = nullptr;
-    uint64_t bytes = 0;
 };
 
 // Scratch of pkt_compare_batch (pktgpu_compare.hip): 256 slots of four device words the blocks add
@@ -161,9 +160,7 @@ struct pkt_ctx {
     HostPipe hp;
     PcapScratch pc;
     PcapWriteScratch pw;
-    FragScratch fr;
-    ReasmScratch rs;
-    IcmpScratch ic;
+    OutScratch fr, rs, ic;  // pkt_frag_batch, pkt_reasm_batch, pkt_icmp_err_batch: one call in flight each
     CompareScratch cmp;
     MaxScratch mx;
     uint32_t window = 0;  // 0 = auto
@@ -270,6 +267,29 @@ struct RepackPiece {
 };
 uint32_t pktgpu_repack_blocks(uint64_t bytes);
 hipError_t pktgpu_repack_launch(const RepackPiece* tab_dev, uint32_t np, uint32_t nblocks, hipStream_t s);
+
+// What the entries of the output-batch contract share (pktgpu_outbatch.hip; the contract: pktgpu_outbatch.hpp).
+// An entry names itself once: its scratch in the ctx and the two names its texts carry.
+struct OutEntry {
+    OutScratch pkt_ctx::*scratch;
+    const char* batch;   // "pkt_X_batch"
+    const char* result;  // "pkt_X_result"
+};
+// The one-block tile scan: blk_bytes / blk_cnt[nb] become their exclusive prefixes; tot (device) and host (the
+// scratch's pinned words) take [total rounded bytes, outputs, overflow], the verdict being out_overflow's unless
+// no_write.  Queued on s; the caller's hipGetLastError covers it.
+void pktgpu_out_scan_launch(uint64_t* blk_bytes, uint64_t* blk_cnt, uint32_t nb, bool no_write, uint64_t out_cap,
+                            uint64_t dst_len, uint64_t* tot, uint64_t* host, hipStream_t s);
+// PKT_ERR_INVALID_ARG with the text "<batch>: <msg>".
+int pktgpu_out_refuse(pkt_ctx_t* ctx, const OutEntry& en, const char* msg);
+// The outcome of the entry's last queued call (the stream has passed it): the totals and the overflow refusal.
+int pktgpu_out_finish(pkt_ctx_t* ctx, const OutEntry& en, uint64_t* bytes_out_total, uint64_t* n_out);
+// The bodies of pkt_X_batch, pkt_X_batch_async and pkt_X_result; queue: the entry's launches with its arguments bound.
+using OutQueue = std::function<int(hipStream_t)>;
+int pktgpu_out_batch(pkt_ctx_t* ctx, const OutEntry& en, const OutQueue& queue, void* stream, uint64_t* bytes_out_total,
+                     uint64_t* n_out);
+int pktgpu_out_batch_async(pkt_ctx_t* ctx, const OutEntry& en, const OutQueue& queue, void* stream);
+int pktgpu_out_result(pkt_ctx_t* ctx, const OutEntry& en, uint64_t* bytes_out_total, uint64_t* n_out);
 
 // The host paths' column export (pktgpu_gather.hip): column range y copies elements [*lo_dev (NULL: 0),
 // min(*hi_dev, cap)) — or [lo_h, hi_h) when hi_dev is NULL — of `sz` bytes from device address src + lo *

@@ -8,9 +8,9 @@
 //                     the packet's plan (16 bytes of scratch: ip_off, per, P, status, chain rows, outputs, length),
 //                     the tile's (outputs, rounded bytes), and the per-status counts merged in LDS and added once
 //                     per block and non-zero status;
-//   fg_scan_kernel    one block: the exclusive prefix of the tile sums, the two totals and the overflow verdict to
-//                     device words and to the ctx's pinned words: what does not fit is known on the device before
-//                     anything is written;
+//   out_scan_kernel   (pktgpu_outbatch.hip, shared with reasm and icmp) one block: the exclusive prefix of the tile
+//                     sums, the two totals and the overflow verdict to device words and to the ctx's pinned words:
+//                     what does not fit is known on the device before anything is written;
 //   fg_emit_kernel    per tile again: a block scan gives each packet's first output index and offset (first[]);
 //                     then each wave spreads the rows of its 64 packets over its lanes (a search in the wave's
 //                     prefix of the output counts), since a packet's rows are closed-form from per and P: out_off,
@@ -36,7 +36,6 @@ namespace {
 
 constexpr uint32_t kGBlock = 256;
 constexpr uint32_t kGWaves = kGBlock / 64;
-constexpr uint32_t kGScanPer = 16;     // tile sums per thread and round of the scan
 constexpr uint32_t kCountBlocks = 1280;  // the counting launches' grid cap (fwd_kernel's, taken over, not measured again)
 constexpr uint32_t kFitsIpo = 0x7FFFFF00u;  // a FITS output's staged ip_off: no header, no second source
 
@@ -83,24 +82,6 @@ __device__ __forceinline__ FragPlan plan_unpack(uint4 v) {
     return p;
 }
 
-// Exclusive prefix of v over the block's threads; total = the block's sum.  (s_w: one word per wave.)
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* s_w, uint64_t& total) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint64_t x = wave_incl_scan(v, lane);
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    uint64_t base = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kGWaves; k++) {
-        const uint64_t t = s_w[k];
-        base += k < wv ? t : 0;
-        total += t;
-    }
-    __syncthreads();  // s_w may be written again
-    return base + x - v;
-}
-
 // the IP header's bytes [S, S + 12) of the slab, which lie inside a packet: the aligned chunk of S, and the next one
 // iff it holds a byte of them (so it lies at or below the slab's last chunk)
 __device__ __forceinline__ void load_hdr12(const uint8_t* slab, uint64_t S, uint32_t h[4]) {
@@ -114,11 +95,8 @@ __device__ __forceinline__ void load_hdr12(const uint8_t* slab, uint64_t S, uint
 __global__ __launch_bounds__(kGBlock) void fg_decide_kernel(GParams P) {
     __shared__ uint32_t s_hits[PKT_FRAG_STATUS_COUNT];
     __shared__ uint64_t s_w[kGWaves];
-    const uint32_t t = threadIdx.x, lane = t & 63u;
-    if (P.hits) {
-        if (t < PKT_FRAG_STATUS_COUNT) s_hits[t] = 0;
-        __syncthreads();
-    }
+    const uint32_t t = threadIdx.x;
+    if (P.hits) hits_zero<PKT_FRAG_STATUS_COUNT>(s_hits, t);
     const uint32_t ntiles = (uint32_t)((P.n + kGBlock - 1) / kGBlock);
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // uniform
         const uint64_t i = (uint64_t)tile * kGBlock + t;
@@ -156,66 +134,15 @@ __global__ __launch_bounds__(kGBlock) void fg_decide_kernel(GParams P) {
         }
         // the tile's sums: at most 256 * 8190 outputs
         uint64_t tc, tb;
-        (void)block_excl_scan(act ? p.nout : 0u, s_w, tc);
-        (void)block_excl_scan(act ? frag_out_bytes(p) : 0u, s_w, tb);
+        (void)block_excl_scan<kGWaves>(act ? p.nout : 0u, s_w, tc);
+        (void)block_excl_scan<kGWaves>(act ? frag_out_bytes(p) : 0u, s_w, tb);
         if (t == 0) {
             P.blk_cnt[tile] = tc;
             P.blk_bytes[tile] = tb;
         }
-        if (P.hits) {
-#pragma unroll
-            for (uint32_t s = 0; s < PKT_FRAG_STATUS_COUNT; s++) {
-                const uint64_t b = __ballot(act && p.st == s);
-                if (lane == 0 && b) atomicAdd(&s_hits[s], (uint32_t)__popcll((unsigned long long)b));
-            }
-        }
+        if (P.hits) hits_add<PKT_FRAG_STATUS_COUNT>(s_hits, t, act, p.st);
     }
-    if (!P.hits) return;
-    __syncthreads();
-    if (t < PKT_FRAG_STATUS_COUNT) {
-        const uint32_t h = s_hits[t];
-        if (h) __hip_atomic_fetch_add(P.hits + t, (uint64_t)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// tot: [total rounded bytes, outputs, overflow] on the device; host: the same three words in pinned memory
-__global__ __launch_bounds__(kGBlock) void fg_scan_kernel(uint64_t* __restrict__ blk_bytes, uint64_t* __restrict__ blk_cnt,
-                                                          uint32_t nb, uint32_t no_write, uint64_t out_cap,
-                                                          uint64_t dst_len, uint64_t* __restrict__ tot,
-                                                          uint64_t* __restrict__ host) {
-    __shared__ uint64_t s_w[kGWaves];
-    uint64_t cb = 0, cc = 0;
-    for (uint64_t base = 0; base < nb; base += (uint64_t)kGBlock * kGScanPer) {
-        const uint64_t i0 = base + (uint64_t)threadIdx.x * kGScanPer;
-        uint64_t b[kGScanPer], c[kGScanPer], sb = 0, sc = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kGScanPer; j++) {
-            const bool in = i0 + j < nb;
-            b[j] = in ? blk_bytes[i0 + j] : 0;
-            c[j] = in ? blk_cnt[i0 + j] : 0;
-            sb += b[j];
-            sc += c[j];
-        }
-        uint64_t tb, tc;
-        uint64_t eb = cb + block_excl_scan(sb, s_w, tb);
-        uint64_t ec = cc + block_excl_scan(sc, s_w, tc);
-#pragma unroll
-        for (uint32_t j = 0; j < kGScanPer; j++) {
-            if (i0 + j < nb) {
-                blk_bytes[i0 + j] = eb;
-                blk_cnt[i0 + j] = ec;
-            }
-            eb += b[j];
-            ec += c[j];
-        }
-        cb += tb;
-        cc += tc;
-    }
-    if (threadIdx.x == 0) {
-        const uint64_t over = !no_write && frag_overflow(cc, cb, out_cap, dst_len) ? 1u : 0u;
-        tot[0] = cb, tot[1] = cc, tot[2] = over;
-        host[0] = cb, host[1] = cc, host[2] = over;
-    }
+    if (P.hits) hits_flush<PKT_FRAG_STATUS_COUNT>(s_hits, t, P.hits);
 }
 
 __global__ __launch_bounds__(kGBlock) void fg_emit_kernel(GParams P) {
@@ -229,8 +156,8 @@ __global__ __launch_bounds__(kGBlock) void fg_emit_kernel(GParams P) {
     const uint4 raw = act ? P.plan[i] : make_uint4(0, 0, 0, 0);
     const FragPlan p = plan_unpack(raw);
     uint64_t tc, tb;
-    const uint64_t q0 = P.blk_cnt[blockIdx.x] + block_excl_scan(p.nout, s_w, tc);
-    const uint64_t o0 = P.blk_bytes[blockIdx.x] + block_excl_scan(frag_out_bytes(p), s_w, tb);
+    const uint64_t q0 = P.blk_cnt[blockIdx.x] + block_excl_scan<kGWaves>(p.nout, s_w, tc);
+    const uint64_t o0 = P.blk_bytes[blockIdx.x] + block_excl_scan<kGWaves>(frag_out_bytes(p), s_w, tb);
     if (act && P.first) P.first[i] = p.nout ? (uint32_t)q0 : PKT_FRAG_NONE;
     if ((P.flags & PKT_FRAG_NO_WRITE) || P.tot[2]) return;  // (uniform) the sizing pass, or the outputs do not fit
     // the wave's rows: at most 64 * 8190
@@ -244,7 +171,9 @@ __global__ __launch_bounds__(kGBlock) void fg_emit_kernel(GParams P) {
     const uint32_t rows = s_pre[wv][64];
     const uint64_t ibase = i - lane;
     for (uint32_t f = lane; f < rows; f += 64) {
-        uint32_t s = 0;  // the packet holding row f: the number of prefix ends at or below f
+        // the packet holding row f: the number of prefix ends at or below f (locate()'s search, written out here and
+        // in the copy kernel: a shared helper taking the prefix as a pointer moved both kernels' code)
+        uint32_t s = 0;
 #pragma unroll
         for (uint32_t st = 32; st; st >>= 1)
             if (s_pre[wv][s + st] <= f) s += st;
@@ -262,22 +191,6 @@ __global__ __launch_bounds__(kGBlock) void fg_emit_kernel(GParams P) {
             if (P.oc_of) P.oc_of[(uint64_t)k * P.out_cap + q] = P.hdr_off[(uint64_t)k * P.n + src];
         }
     }
-}
-
-__device__ __forceinline__ Le128 le128(const uint32_t o[4]) {
-    return Le128{(uint64_t)o[0] | (uint64_t)o[1] << 32, (uint64_t)o[2] | (uint64_t)o[3] << 32};
-}
-
-// the 16 slab bytes from `pos` on, pos < slab_len: the second aligned chunk is clamped to the slab's last one (what
-// it then gives lies past the slab, so past every packet: the caller masks it off)
-__device__ __forceinline__ Le128 load16(const uint8_t* slab, uint64_t pos, uint64_t last16) {
-    const uint64_t A = pos & ~(uint64_t)15;
-    const uint64_t B = A + 16 > last16 ? last16 : A + 16;
-    const uint4 v0 = *reinterpret_cast<const uint4*>(slab + A);
-    const uint4 v1 = *reinterpret_cast<const uint4*>(slab + B);
-    uint32_t o[4];
-    take16(v0, v1, (uint32_t)pos & 15u, o);
-    return le128(o);
 }
 
 __global__ __launch_bounds__(kGBlock) void fg_copy_kernel(GParams P) {
@@ -324,7 +237,7 @@ __global__ __launch_bounds__(kGBlock) void fg_copy_kernel(GParams P) {
     if (lane == 0) s_pre[wv][0] = 0;
     wave_sync();
     const uint32_t total = s_pre[wv][64];  // at most 64 * 4096
-    const uint64_t last16 = P.src.slab_len ? ((P.src.slab_len + 15) & ~(uint64_t)15) - 16 : 0;
+    const uint64_t last16 = slab_last16(P.src);
     for (uint32_t f = lane; f < total; f += 64) {
         uint32_t s = 0;
 #pragma unroll
@@ -362,12 +275,7 @@ __global__ __launch_bounds__(kGBlock) void fg_copy_kernel(GParams P) {
     }
 }
 
-uint64_t round16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
-
-int fg_refuse(pkt_ctx* ctx, const char* msg) {
-    if (ctx) ctx->err = std::string("pkt_frag_batch: ") + msg;
-    return PKT_ERR_INVALID_ARG;
-}
+constexpr OutEntry kFragEntry{&pkt_ctx::fr, "pkt_frag_batch", "pkt_frag_result"};
 
 // The launches, queued on s.  The totals and the verdict arrive in ctx->fr.ctl once the stream has passed them.
 int fg_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
@@ -376,9 +284,10 @@ int fg_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
              uint32_t* src_index, uint16_t* frag_index, const pkt_chain_t* out_chain, uint64_t* hits, hipStream_t s) {
     if (!ctx) return PKT_ERR_INVALID_ARG;
     if (const char* msg = frag_call_error(b, chain, which_ip, flags, mtu, mtu_all, dst, out_cap, out_off, out_len, hits, true))
-        return fg_refuse(ctx, msg);
-    FragScratch& fr = ctx->fr;
-    if (fr.pending) return fg_refuse(ctx, "a queued call's result has not been taken on this ctx (pkt_frag_result)");
+        return pktgpu_out_refuse(ctx, kFragEntry, msg);
+    OutScratch& fr = ctx->fr;
+    if (fr.pending)
+        return pktgpu_out_refuse(ctx, kFragEntry, "a queued call's result has not been taken on this ctx (pkt_frag_result)");
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     const bool write = !(flags & PKT_FRAG_NO_WRITE);
@@ -388,13 +297,7 @@ int fg_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
     const uint64_t o_bytes = 64, o_cnt = o_bytes + round16(8ull * nb), o_plan = o_cnt + round16(8ull * nb);
     const uint64_t o_ksrc = o_plan + 16 * n, o_kfrag = o_ksrc + (src_index || !write ? 0 : round16(4 * out_cap));
     const uint64_t need = o_kfrag + (frag_index || !write ? 0 : round16(2 * out_cap));
-    if (need > fr.bytes) {
-        if (fr.buf) (void)hipFree(fr.buf);  // (waits for the device: no earlier call still uses it)
-        fr.buf = nullptr;
-        fr.bytes = 0;
-        if ((e = hipMalloc(&fr.buf, need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pkt_frag_batch)");
-        fr.bytes = need;
-    }
+    if ((e = fr.reserve(need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pkt_frag_batch)");
     if ((e = fr.ensure(64)) != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (pkt_frag_batch)");
     char* p = static_cast<char*>(fr.buf);
     GParams P{};
@@ -426,32 +329,19 @@ int fg_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
         P.frag_index = frag_index;
         P.k_src = src_index ? src_index : reinterpret_cast<uint32_t*>(p + o_ksrc);
         P.k_frag = frag_index ? frag_index : reinterpret_cast<uint16_t*>(p + o_kfrag);
-        if (out_chain) {
-            P.oc_nh = const_cast<uint8_t*>(out_chain->n_hdrs);
-            P.oc_ty = const_cast<uint8_t*>(out_chain->hdr_type);
-            P.oc_of = const_cast<uint16_t*>(out_chain->hdr_off);
-        }
+        const OutChainCols oc = out_chain_cols(out_chain);
+        P.oc_nh = oc.nh, P.oc_ty = oc.ty, P.oc_of = oc.of;
     }
     fr.ctl[0] = fr.ctl[1] = fr.ctl[2] = 0;
     if (nb) {
         const uint32_t grid = hits && nb > kCountBlocks ? kCountBlocks : nb;
         hipLaunchKernelGGL(fg_decide_kernel, dim3(grid), dim3(kGBlock), 0, s, P);
     }
-    hipLaunchKernelGGL(fg_scan_kernel, dim3(1), dim3(kGBlock), 0, s, P.blk_bytes, P.blk_cnt, nb, write ? 0u : 1u, out_cap,
-                       dst_len, P.tot, fr.ctl_dev);
+    pktgpu_out_scan_launch(P.blk_bytes, P.blk_cnt, nb, !write, out_cap, dst_len, P.tot, fr.ctl_dev, s);
     if (nb && (write || first)) hipLaunchKernelGGL(fg_emit_kernel, dim3(nb), dim3(kGBlock), 0, s, P);
     if (write)
         hipLaunchKernelGGL(fg_copy_kernel, dim3((unsigned)((out_cap + kGBlock - 1) / kGBlock)), dim3(kGBlock), 0, s, P);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "pkt_frag_batch launch");
-    return PKT_SUCCESS;
-}
-
-// The outcome of the last fg_queue (the stream has passed it).
-int fg_finish(pkt_ctx_t* ctx, uint64_t* bytes_out_total, uint64_t* n_out) {
-    const FragScratch& fr = ctx->fr;
-    if (bytes_out_total) *bytes_out_total = fr.ctl[0];
-    if (n_out) *n_out = fr.ctl[1];
-    if (fr.ctl[2]) return fg_refuse(ctx, "the outputs do not fit out_cap / dst_len (the totals are the capacity needed)");
     return PKT_SUCCESS;
 }
 
@@ -464,15 +354,11 @@ int pkt_frag_batch(pkt_ctx_t* ctx, const pkt_batch_t* batch, const pkt_chain_t* 
                    uint32_t* first, uint8_t* dst, uint64_t dst_len, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len,
                    uint32_t* src_index, uint16_t* frag_index, const pkt_chain_t* out_chain, uint64_t* hits,
                    uint64_t* bytes_out_total, uint64_t* n_out, void* stream) {
-    if (bytes_out_total) *bytes_out_total = 0;
-    if (n_out) *n_out = 0;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int rc = fg_queue(ctx, batch, chain, which_ip, flags, mtu, mtu_all, select, status, nfrag, first, dst, dst_len,
-                            out_cap, out_off, out_len, src_index, frag_index, out_chain, hits, s);
-    if (rc != PKT_SUCCESS) return rc;
-    const hipError_t e = hipStreamSynchronize(s);  // the one host wait, for the totals
-    if (e != hipSuccess) return hip_fail(ctx, e, "pkt_frag_batch");
-    return fg_finish(ctx, bytes_out_total, n_out);
+    const auto queue = [&](hipStream_t s) {
+        return fg_queue(ctx, batch, chain, which_ip, flags, mtu, mtu_all, select, status, nfrag, first, dst, dst_len, out_cap,
+                        out_off, out_len, src_index, frag_index, out_chain, hits, s);
+    };
+    return pktgpu_out_batch(ctx, kFragEntry, queue, stream, bytes_out_total, n_out);
 }
 
 int pkt_frag_batch_async(pkt_ctx_t* ctx, const pkt_batch_t* batch, const pkt_chain_t* chain, uint32_t which_ip,
@@ -480,23 +366,15 @@ int pkt_frag_batch_async(pkt_ctx_t* ctx, const pkt_batch_t* batch, const pkt_cha
                          uint32_t* nfrag, uint32_t* first, uint8_t* dst, uint64_t dst_len, uint64_t out_cap,
                          uint64_t* out_off, uint32_t* out_len, uint32_t* src_index, uint16_t* frag_index,
                          const pkt_chain_t* out_chain, uint64_t* hits, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int rc = fg_queue(ctx, batch, chain, which_ip, flags, mtu, mtu_all, select, status, nfrag, first, dst, dst_len,
-                            out_cap, out_off, out_len, src_index, frag_index, out_chain, hits, s);
-    if (rc != PKT_SUCCESS) return rc;
-    ctx->fr.mark(s);
-    return PKT_SUCCESS;
+    const auto queue = [&](hipStream_t s) {
+        return fg_queue(ctx, batch, chain, which_ip, flags, mtu, mtu_all, select, status, nfrag, first, dst, dst_len, out_cap,
+                        out_off, out_len, src_index, frag_index, out_chain, hits, s);
+    };
+    return pktgpu_out_batch_async(ctx, kFragEntry, queue, stream);
 }
 
 int pkt_frag_result(pkt_ctx_t* ctx, uint64_t* bytes_out_total, uint64_t* n_out) {
-    if (bytes_out_total) *bytes_out_total = 0;
-    if (n_out) *n_out = 0;
-    if (!ctx) return PKT_ERR_INVALID_ARG;
-    FragScratch& fr = ctx->fr;
-    if (!fr.pending) return fail(ctx, PKT_ERR_INVALID_ARG, "pkt_frag_result: no call queued on this ctx");
-    const hipError_t e = fr.take();
-    if (e != hipSuccess) return hip_fail(ctx, e, "pkt_frag_result");
-    return fg_finish(ctx, bytes_out_total, n_out);
+    return pktgpu_out_result(ctx, kFragEntry, bytes_out_total, n_out);
 }
 
 }  // extern "C"

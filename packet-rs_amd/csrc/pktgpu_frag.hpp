@@ -9,10 +9,9 @@
 
 #include "pktgpu_batch.hpp"
 #include "pktgpu_fwd.hpp"
+#include "pktgpu_outbatch.hpp"
 
 constexpr uint32_t kFragFlags = PKT_FRAG_ONLY_SPLIT | PKT_FRAG_NO_WRITE;
-
-PKT_HD uint32_t frag_round16(uint32_t x) { return (x + 15u) & ~15u; }
 
 // A source packet's plan: what the emit and copy steps need, none of it read from the packet again except the header.
 struct FragPlan {
@@ -107,12 +106,12 @@ PKT_HD uint32_t frag_out_len(const FragPlan& p, uint32_t j) {
     return p.ipo + 20u + (j + 1u < p.nout ? p.per : p.pay - (p.nout - 1u) * p.per);
 }
 PKT_HD uint64_t frag_out_rel(const FragPlan& p, uint32_t j) {
-    return p.st == PKT_FRAG_SPLIT ? (uint64_t)j * frag_round16(p.ipo + 20u + p.per) : 0u;
+    return p.st == PKT_FRAG_SPLIT ? (uint64_t)j * out_round16(p.ipo + 20u + p.per) : 0u;
 }
 // the rounded bytes of all the packet's outputs (at most 8190 * 65536: it fits 32 bits, kept in 64)
 PKT_HD uint64_t frag_out_bytes(const FragPlan& p) {
     if (!p.nout) return 0;
-    return frag_out_rel(p, p.nout - 1u) + frag_round16(frag_out_len(p, p.nout - 1u));
+    return frag_out_rel(p, p.nout - 1u) + out_round16(frag_out_len(p, p.nout - 1u));
 }
 
 // Fragment j's IPv4 bytes 0..11 from the source's (h, little-endian dwords as above): the total length, the flags and
@@ -131,12 +130,7 @@ PKT_HD void frag_header(const FragPlan& p, uint32_t j, const uint32_t h[3], uint
     o[2] = (h[2] & 0xFFFFu) | fwd_be16(hc2) << 16;
 }
 
-// did the outputs fit what the caller gave? (the device decides it in its scan kernel, the host after its first pass)
-PKT_HD bool frag_overflow(uint64_t n_out, uint64_t bytes, uint64_t out_cap, uint64_t dst_len) {
-    return n_out > out_cap || n_out >= (1ull << 32) || bytes > dst_len;
-}
-
-// ---- the refusals both entry points share: the text (after "pkt_frag_batch: "), or nullptr.
+// ---- the refusals both entry points share: the text (after "pkt_frag_batch: "), or nullptr; the contract's own last.
 // device: pkt_frag_batch (the slab's alignment rule); else pkt_frag_host.
 inline const char* frag_call_error(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
                                    const uint16_t* mtu, uint32_t mtu_all, const uint8_t* dst, uint64_t out_cap,
@@ -147,18 +141,6 @@ inline const char* frag_call_error(const pkt_batch_t* b, const pkt_chain_t* chai
     if (which_ip >= PKT_MAX_HDRS && which_ip != PKT_FLOW_LAST) return "which_ip is neither below 16 nor PKT_FLOW_LAST";
     if (mtu_all > 65535u) return "mtu_all above 65535";
     if ((uintptr_t)mtu & 1) return "mtu not 2-byte aligned";
-    if ((uintptr_t)hits & 7) return "hits not 8-byte aligned";
-    if ((uintptr_t)dst & 15) return "dst not 16-byte aligned";
-    if ((uintptr_t)out_off & 7) return "out_off not 8-byte aligned";
-    if (!(flags & PKT_FRAG_NO_WRITE)) {
-        if (!dst || !out_off || !out_len) return "null dst, out_off or out_len without PKT_FRAG_NO_WRITE";
-        if (out_cap == 0 || out_cap >= (1ull << 32)) return "out_cap is 0 or >= 2^32";
-    }
-    if (b->n) {
-        if (!chain->n_hdrs || !chain->hdr_type || !chain->hdr_off) return "null chain column";
-        const char* msg = device ? batch_slab16_error(b) : batch_null_slab(b) ? "null slab" : nullptr;
-        if (msg) return msg;
-        return batch_index_error(b);
-    }
-    return nullptr;
+    return out_call_error(b, chain, flags & PKT_FRAG_NO_WRITE, "null dst, out_off or out_len without PKT_FRAG_NO_WRITE", dst,
+                          out_cap, out_off, out_len, hits, device);
 }

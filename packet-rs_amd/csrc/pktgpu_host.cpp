@@ -1147,10 +1147,8 @@ int pkt_frag_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which
     if (bytes_out_total) *bytes_out_total = bytes;
     if (n_out) *n_out = q;
     if (!write) return PKT_SUCCESS;
-    if (frag_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
-    uint8_t* oc_nh = out_chain ? const_cast<uint8_t*>(out_chain->n_hdrs) : nullptr;
-    uint8_t* oc_ty = out_chain ? const_cast<uint8_t*>(out_chain->hdr_type) : nullptr;
-    uint16_t* oc_of = out_chain ? const_cast<uint16_t*>(out_chain->hdr_off) : nullptr;
+    if (out_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
+    const OutChainCols oc = out_chain_cols(out_chain);
     q = 0;
     uint64_t pos = 0;
     for (uint64_t i = 0; i < n; i++) {
@@ -1176,26 +1174,20 @@ int pkt_frag_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which
             } else if (ol) {
                 memcpy(d, s, ol);
             }
-            memset(d + ol, 0, frag_round16(ol) - ol);
+            memset(d + ol, 0, out_round16(ol) - ol);
             out_off[q] = pos;
             out_len[q] = ol;
             if (src_index) src_index[q] = (uint32_t)i;
             if (frag_index) frag_index[q] = (uint16_t)j;
-            if (oc_nh) oc_nh[q] = (uint8_t)p.nh;
+            if (oc.nh) oc.nh[q] = (uint8_t)p.nh;
             for (uint32_t r = 0; r < p.nh; r++) {
-                if (oc_ty) oc_ty[r * out_cap + q] = chain->hdr_type[r * n + i];
-                if (oc_of) oc_of[r * out_cap + q] = chain->hdr_off[r * n + i];
+                if (oc.ty) oc.ty[r * out_cap + q] = chain->hdr_type[r * n + i];
+                if (oc.of) oc.of[r * out_cap + q] = chain->hdr_off[r * n + i];
             }
-            pos += frag_round16(ol);
+            pos += out_round16(ol);
         }
     }
-    for (; q < out_cap; q++) {
-        out_off[q] = 0;
-        out_len[q] = 0;
-        if (src_index) src_index[q] = PKT_FRAG_NONE;
-        if (frag_index) frag_index[q] = 0;
-        if (oc_nh) oc_nh[q] = 0;
-    }
+    out_empty_tail(q, out_cap, out_off, out_len, src_index, frag_index, oc.nh);
     return PKT_SUCCESS;
 }
 
@@ -1294,7 +1286,7 @@ int reasm_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip
         const uint32_t ol = out_len_of(i);
         if (!ol) continue;
         oq[i] = (uint32_t)q++;
-        bytes += frag_round16(ol);
+        bytes += out_round16(ol);
     }
     for (uint64_t i = 0; i < n; i++) {
         const uint32_t st = rec[i].st;
@@ -1305,10 +1297,8 @@ int reasm_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip
     if (bytes_out_total) *bytes_out_total = bytes;
     if (n_out) *n_out = q;
     if (!write) return PKT_SUCCESS;
-    if (frag_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
-    uint8_t* oc_nh = out_chain ? const_cast<uint8_t*>(out_chain->n_hdrs) : nullptr;
-    uint8_t* oc_ty = out_chain ? const_cast<uint8_t*>(out_chain->hdr_type) : nullptr;
-    uint16_t* oc_of = out_chain ? const_cast<uint16_t*>(out_chain->hdr_off) : nullptr;
+    if (out_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
+    const OutChainCols oc = out_chain_cols(out_chain);
     uint64_t pos = 0;
     q = 0;
     for (uint64_t i = 0; i < n; i++) {
@@ -1338,27 +1328,21 @@ int reasm_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip
                 memcpy(d + ipo0 + 20u + m.s, src.slab + pkt_off(src, order[k]) + m.ipo + 20u, m.len);
             }
         }
-        memset(d + ol, 0, frag_round16(ol) - ol);
+        memset(d + ol, 0, out_round16(ol) - ol);
         out_off[q] = pos;
         out_len[q] = ol;
         if (src_index) src_index[q] = (uint32_t)i;
         if (nfrag) nfrag[q] = members;
         const uint32_t nh = rec[rows_of].nh;
-        if (oc_nh) oc_nh[q] = (uint8_t)nh;
+        if (oc.nh) oc.nh[q] = (uint8_t)nh;
         for (uint32_t r = 0; r < nh; r++) {
-            if (oc_ty) oc_ty[r * out_cap + q] = chain->hdr_type[r * n + rows_of];
-            if (oc_of) oc_of[r * out_cap + q] = chain->hdr_off[r * n + rows_of];
+            if (oc.ty) oc.ty[r * out_cap + q] = chain->hdr_type[r * n + rows_of];
+            if (oc.of) oc.of[r * out_cap + q] = chain->hdr_off[r * n + rows_of];
         }
-        pos += frag_round16(ol);
+        pos += out_round16(ol);
         q++;
     }
-    for (; q < out_cap; q++) {
-        out_off[q] = 0;
-        out_len[q] = 0;
-        if (src_index) src_index[q] = PKT_REASM_NONE;
-        if (nfrag) nfrag[q] = 0;
-        if (oc_nh) oc_nh[q] = 0;
-    }
+    out_empty_tail(q, out_cap, out_off, out_len, src_index, nfrag, oc.nh);
     return PKT_SUCCESS;
 }
 
@@ -1437,16 +1421,14 @@ int pkt_icmp_err_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t w
         if (hits) hits[p.st] += 1;
         if (sent) {
             q += 1;
-            bytes += frag_round16(icmp_out_len(p));
+            bytes += out_round16(icmp_out_len(p));
         }
     }
     if (bytes_out_total) *bytes_out_total = bytes;
     if (n_out) *n_out = q;
     if (!write) return PKT_SUCCESS;
-    if (frag_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
-    uint8_t* oc_nh = out_chain ? const_cast<uint8_t*>(out_chain->n_hdrs) : nullptr;
-    uint8_t* oc_ty = out_chain ? const_cast<uint8_t*>(out_chain->hdr_type) : nullptr;
-    uint16_t* oc_of = out_chain ? const_cast<uint16_t*>(out_chain->hdr_off) : nullptr;
+    if (out_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
+    const OutChainCols oc = out_chain_cols(out_chain);
     q = 0;
     uint64_t pos = 0;
     for (uint64_t i = 0; i < n; i++) {
@@ -1468,29 +1450,24 @@ int pkt_icmp_err_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t w
         const uint32_t c = icmp_csum(p, part, qs);
         d[P + H + 2u] = (uint8_t)(c >> 8);
         d[P + H + 3u] = (uint8_t)c;
-        memset(d + ol, 0, frag_round16(ol) - ol);
+        memset(d + ol, 0, out_round16(ol) - ol);
         out_off[q] = pos;
         out_len[q] = ol;
         if (src_index) src_index[q] = (uint32_t)i;
         const uint32_t rows = p.e_ip - p.e_eth + 1u;
-        if (oc_nh) oc_nh[q] = (uint8_t)(rows + 1u > PKT_MAX_HDRS ? PKT_MAX_HDRS : rows + 1u);
+        if (oc.nh) oc.nh[q] = (uint8_t)(rows + 1u > PKT_MAX_HDRS ? PKT_MAX_HDRS : rows + 1u);
         for (uint32_t r = 0; r < rows; r++) {
-            if (oc_ty) oc_ty[r * out_cap + q] = chain->hdr_type[(p.e_eth + r) * n + i];
-            if (oc_of) oc_of[r * out_cap + q] = (uint16_t)(chain->hdr_off[(p.e_eth + r) * n + i] - p.eth);
+            if (oc.ty) oc.ty[r * out_cap + q] = chain->hdr_type[(p.e_eth + r) * n + i];
+            if (oc.of) oc.of[r * out_cap + q] = (uint16_t)(chain->hdr_off[(p.e_eth + r) * n + i] - p.eth);
         }
         if (rows < PKT_MAX_HDRS) {
-            if (oc_ty) oc_ty[rows * out_cap + q] = PKT_HDR_ICMP;
-            if (oc_of) oc_of[rows * out_cap + q] = (uint16_t)(P + H);
+            if (oc.ty) oc.ty[rows * out_cap + q] = PKT_HDR_ICMP;
+            if (oc.of) oc.of[rows * out_cap + q] = (uint16_t)(P + H);
         }
-        pos += frag_round16(ol);
+        pos += out_round16(ol);
         q++;
     }
-    for (; q < out_cap; q++) {
-        out_off[q] = 0;
-        out_len[q] = 0;
-        if (src_index) src_index[q] = PKT_ICMPE_NONE;
-        if (oc_nh) oc_nh[q] = 0;
-    }
+    out_empty_tail(q, out_cap, out_off, out_len, src_index, static_cast<uint8_t*>(nullptr), oc.nh);
     return PKT_SUCCESS;
 }
 

@@ -9,8 +9,8 @@
 //                     destination's first byte (take16), the decision of pktgpu_icmp.hpp.  Out: status, the packet's
 //                     plan (32 bytes of scratch), the tile's (outputs, rounded bytes), and the per-status counts
 //                     merged in LDS and added once per block and non-zero status;
-//   ic_scan_kernel    one block: the exclusive prefix of the tile sums, the two totals and the overflow verdict to
-//                     device words and to the ctx's pinned words (fg_scan_kernel's job; a kernel of this file's own);
+//   out_scan_kernel   (pktgpu_outbatch.hip, shared with frag and reasm) one block: the exclusive prefix of the tile
+//                     sums, the two totals and the overflow verdict to device words and to the ctx's pinned words;
 //   ic_build_kernel   per tile again: a block scan gives each answered packet its output index and offset; the lane
 //                     writes out_index and its output's row of the per-output arrays and stages the output in LDS
 //                     (destination, source, offsets, Q and the 28 / 48 header bytes of icmp_headers, the ICMP
@@ -36,7 +36,6 @@ namespace {
 
 constexpr uint32_t kIBlock = 256;
 constexpr uint32_t kIWaves = kIBlock / 64;
-constexpr uint32_t kIScanPer = 16;       // tile sums per thread and round of the scan
 constexpr uint32_t kCountBlocks = 1280;  // the counting launch's grid cap (fwd_kernel's, taken over, not measured again)
 
 struct IParams {
@@ -88,43 +87,6 @@ __device__ __forceinline__ IcmpPlan plan_unpack(uint4 a, uint4 b) {
     return p;
 }
 
-// Exclusive prefix of v over the block's threads; total = the block's sum.  (s_w: one word per wave.)
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* s_w, uint64_t& total) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint64_t x = wave_incl_scan(v, lane);
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    uint64_t base = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kIWaves; k++) {
-        const uint64_t t = s_w[k];
-        base += k < wv ? t : 0;
-        total += t;
-    }
-    __syncthreads();  // s_w may be written again
-    return base + x - v;
-}
-
-// the slab's last aligned 16-byte chunk (slab_len > 0 wherever a packet has a byte)
-__device__ __forceinline__ uint64_t slab_last16(const BatchSrc& s) {
-    return s.slab_len ? ((s.slab_len + 15) & ~(uint64_t)15) - 16 : 0;
-}
-
-// the 16 slab bytes from `pos` on, pos < slab_len, as four little-endian dwords: the second aligned chunk is clamped
-// to the slab's last one (what it then gives lies past the slab, so past every packet: the caller does not use it)
-__device__ __forceinline__ void load16w(const uint8_t* slab, uint64_t pos, uint64_t last16, uint32_t o[4]) {
-    const uint64_t A = pos & ~(uint64_t)15;
-    const uint64_t B = A + 16 > last16 ? last16 : A + 16;
-    const uint4 v0 = *reinterpret_cast<const uint4*>(slab + A);
-    const uint4 v1 = *reinterpret_cast<const uint4*>(slab + B);
-    take16(v0, v1, (uint32_t)pos & 15u, o);
-}
-__device__ __forceinline__ Le128 load16(const uint8_t* slab, uint64_t pos, uint64_t last16) {
-    uint32_t o[4];
-    load16w(slab, pos, last16, o);
-    return Le128{(uint64_t)o[0] | (uint64_t)o[1] << 32, (uint64_t)o[2] | (uint64_t)o[3] << 32};
-}
 // the slab byte at pos < slab_len, out of its aligned chunk
 __device__ __forceinline__ uint32_t load_byte(const uint8_t* slab, uint64_t pos) {
     const uint4 v = *reinterpret_cast<const uint4*>(slab + (pos & ~(uint64_t)15));
@@ -137,11 +99,8 @@ __global__ __launch_bounds__(kIBlock) void ic_decide_kernel(IArgs A) {
     const IParams& P = A.P;
     __shared__ uint32_t s_hits[PKT_ICMPE_STATUS_COUNT];
     __shared__ uint64_t s_w[kIWaves];
-    const uint32_t t = threadIdx.x, lane = t & 63u;
-    if (P.hits) {
-        if (t < PKT_ICMPE_STATUS_COUNT) s_hits[t] = 0;
-        __syncthreads();
-    }
+    const uint32_t t = threadIdx.x;
+    if (P.hits) hits_zero<PKT_ICMPE_STATUS_COUNT>(s_hits, t);
     const uint32_t ntiles = (uint32_t)((P.n + kIBlock - 1) / kIBlock);
     const uint64_t last16 = slab_last16(P.src);
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // uniform
@@ -192,66 +151,15 @@ __global__ __launch_bounds__(kIBlock) void ic_decide_kernel(IArgs A) {
         }
         const bool sent = act && p.st == PKT_ICMPE_SENT;
         uint64_t tc, tb;
-        (void)block_excl_scan(sent ? 1u : 0u, s_w, tc);
-        (void)block_excl_scan(sent ? frag_round16(icmp_out_len(p)) : 0u, s_w, tb);
+        (void)block_excl_scan<kIWaves>(sent ? 1u : 0u, s_w, tc);
+        (void)block_excl_scan<kIWaves>(sent ? out_round16(icmp_out_len(p)) : 0u, s_w, tb);
         if (t == 0) {
             P.blk_cnt[tile] = tc;
             P.blk_bytes[tile] = tb;
         }
-        if (P.hits) {
-#pragma unroll
-            for (uint32_t s = 0; s < PKT_ICMPE_STATUS_COUNT; s++) {
-                const uint64_t bl = __ballot(act && p.st == s);
-                if (lane == 0 && bl) atomicAdd(&s_hits[s], (uint32_t)__popcll((unsigned long long)bl));
-            }
-        }
+        if (P.hits) hits_add<PKT_ICMPE_STATUS_COUNT>(s_hits, t, act, p.st);
     }
-    if (!P.hits) return;
-    __syncthreads();
-    if (t < PKT_ICMPE_STATUS_COUNT) {
-        const uint32_t h = s_hits[t];
-        if (h) __hip_atomic_fetch_add(P.hits + t, (uint64_t)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// tot: [total rounded bytes, outputs, overflow] on the device; host: the same three words in pinned memory
-__global__ __launch_bounds__(kIBlock) void ic_scan_kernel(uint64_t* __restrict__ blk_bytes, uint64_t* __restrict__ blk_cnt,
-                                                          uint32_t nb, uint32_t no_write, uint64_t out_cap,
-                                                          uint64_t dst_len, uint64_t* __restrict__ tot,
-                                                          uint64_t* __restrict__ host) {
-    __shared__ uint64_t s_w[kIWaves];
-    uint64_t cb = 0, cc = 0;
-    for (uint64_t base = 0; base < nb; base += (uint64_t)kIBlock * kIScanPer) {
-        const uint64_t i0 = base + (uint64_t)threadIdx.x * kIScanPer;
-        uint64_t b[kIScanPer], c[kIScanPer], sb = 0, sc = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kIScanPer; j++) {
-            const bool in = i0 + j < nb;
-            b[j] = in ? blk_bytes[i0 + j] : 0;
-            c[j] = in ? blk_cnt[i0 + j] : 0;
-            sb += b[j];
-            sc += c[j];
-        }
-        uint64_t tb, tc;
-        uint64_t eb = cb + block_excl_scan(sb, s_w, tb);
-        uint64_t ec = cc + block_excl_scan(sc, s_w, tc);
-#pragma unroll
-        for (uint32_t j = 0; j < kIScanPer; j++) {
-            if (i0 + j < nb) {
-                blk_bytes[i0 + j] = eb;
-                blk_cnt[i0 + j] = ec;
-            }
-            eb += b[j];
-            ec += c[j];
-        }
-        cb += tb;
-        cc += tc;
-    }
-    if (threadIdx.x == 0) {
-        const uint64_t over = !no_write && frag_overflow(cc, cb, out_cap, dst_len) ? 1u : 0u;
-        tot[0] = cb, tot[1] = cc, tot[2] = over;
-        host[0] = cb, host[1] = cc, host[2] = over;
-    }
+    if (P.hits) hits_flush<PKT_ICMPE_STATUS_COUNT>(s_hits, t, P.hits);
 }
 
 __device__ __forceinline__ Le128 le_and(Le128 a, Le128 m) { return Le128{a.lo & m.lo, a.hi & m.hi}; }
@@ -336,8 +244,8 @@ __global__ __launch_bounds__(kIBlock) void ic_build_kernel(IArgs A) {
     const bool sent = act && p.st == PKT_ICMPE_SENT;
     const uint32_t ol = sent ? icmp_out_len(p) : 0u;
     uint64_t tc, tb;
-    const uint64_t q = P.blk_cnt[blockIdx.x] + block_excl_scan(sent ? 1u : 0u, s_w, tc);
-    const uint64_t o0 = P.blk_bytes[blockIdx.x] + block_excl_scan(frag_round16(ol), s_w, tb);
+    const uint64_t q = P.blk_cnt[blockIdx.x] + block_excl_scan<kIWaves>(sent ? 1u : 0u, s_w, tc);
+    const uint64_t o0 = P.blk_bytes[blockIdx.x] + block_excl_scan<kIWaves>(out_round16(ol), s_w, tb);
     if (act && P.out_index) P.out_index[i] = sent ? (uint32_t)q : PKT_ICMPE_NONE;
     if (!write) return;  // (uniform)
     const uint32_t H = icmp_hlen(p), Pp = p.ipo - p.eth;
@@ -375,7 +283,9 @@ __global__ __launch_bounds__(kIBlock) void ic_build_kernel(IArgs A) {
     const uint32_t total = s_pre[wv][64];  // at most 64 * 8192
     const uint64_t last16 = slab_last16(P.src);
     for (uint32_t f = lane; f < total; f += 64) {
-        uint32_t s = 0;  // the output holding chunk f: the number of prefix ends at or below f
+        // the output holding chunk f: the number of prefix ends at or below f (locate()'s search, written out: a
+        // shared helper taking the prefix as a pointer moved this kernel's code)
+        uint32_t s = 0;
 #pragma unroll
         for (uint32_t st = 32; st; st >>= 1)
             if (s_pre[wv][s + st] <= f) s += st;
@@ -406,12 +316,7 @@ __global__ __launch_bounds__(kIBlock) void ic_build_kernel(IArgs A) {
     }
 }
 
-uint64_t round16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
-
-int ic_refuse(pkt_ctx* ctx, const char* msg) {
-    if (ctx) ctx->err = std::string("pkt_icmp_err_batch: ") + msg;
-    return PKT_ERR_INVALID_ARG;
-}
+constexpr OutEntry kIcmpEntry{&pkt_ctx::ic, "pkt_icmp_err_batch", "pkt_icmp_err_result"};
 
 // The launches, queued on s.  The totals and the verdict arrive in ctx->ic.ctl once the stream has passed them.
 int ic_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
@@ -422,9 +327,10 @@ int ic_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
     if (!ctx) return PKT_ERR_INVALID_ARG;
     if (const char* msg = icmp_call_error(b, chain, which_ip, flags, cfg, code_all, mtu, mtu_all, dst, out_cap, out_off,
                                           out_len, hits, true))
-        return ic_refuse(ctx, msg);
-    IcmpScratch& ic = ctx->ic;
-    if (ic.pending) return ic_refuse(ctx, "a queued call's result has not been taken on this ctx (pkt_icmp_err_result)");
+        return pktgpu_out_refuse(ctx, kIcmpEntry, msg);
+    OutScratch& ic = ctx->ic;
+    if (ic.pending)
+        return pktgpu_out_refuse(ctx, kIcmpEntry, "a queued call's result has not been taken on this ctx (pkt_icmp_err_result)");
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     const bool write = !(flags & PKT_ICMPE_NO_WRITE);
@@ -433,13 +339,7 @@ int ic_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
     const uint32_t nb = (uint32_t)((n + kIBlock - 1) / kIBlock);
     const uint64_t o_bytes = 64, o_cnt = o_bytes + round16(8ull * nb), o_plan = o_cnt + round16(8ull * nb);
     const uint64_t need = o_plan + 32 * n;
-    if (need > ic.bytes) {
-        if (ic.buf) (void)hipFree(ic.buf);  // (waits for the device: no earlier call still uses it)
-        ic.buf = nullptr;
-        ic.bytes = 0;
-        if ((e = hipMalloc(&ic.buf, need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pkt_icmp_err_batch)");
-        ic.bytes = need;
-    }
+    if ((e = ic.reserve(need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pkt_icmp_err_batch)");
     if ((e = ic.ensure(64)) != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (pkt_icmp_err_batch)");
     char* p = static_cast<char*>(ic.buf);
     IArgs A{};
@@ -471,33 +371,20 @@ int ic_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
         P.out_off = out_off;
         P.out_len = out_len;
         P.src_index = src_index;
-        if (out_chain) {
-            P.oc_nh = const_cast<uint8_t*>(out_chain->n_hdrs);
-            P.oc_ty = const_cast<uint8_t*>(out_chain->hdr_type);
-            P.oc_of = const_cast<uint16_t*>(out_chain->hdr_off);
-        }
+        const OutChainCols oc = out_chain_cols(out_chain);
+        P.oc_nh = oc.nh, P.oc_ty = oc.ty, P.oc_of = oc.of;
     }
     ic.ctl[0] = ic.ctl[1] = ic.ctl[2] = 0;
     if (nb) {
         const uint32_t grid = hits && nb > kCountBlocks ? kCountBlocks : nb;
         hipLaunchKernelGGL(ic_decide_kernel, dim3(grid), dim3(kIBlock), 0, s, A);
     }
-    hipLaunchKernelGGL(ic_scan_kernel, dim3(1), dim3(kIBlock), 0, s, P.blk_bytes, P.blk_cnt, nb, write ? 0u : 1u, out_cap,
-                       dst_len, P.tot, ic.ctl_dev);
+    pktgpu_out_scan_launch(P.blk_bytes, P.blk_cnt, nb, !write, out_cap, dst_len, P.tot, ic.ctl_dev, s);
     // a block per tile of sources, and enough blocks for the empty tail of the per-output arrays
     const uint64_t tail_blocks = (out_cap + kIBlock - 1) / kIBlock;
     const uint32_t grid = (uint32_t)(write && tail_blocks > nb ? tail_blocks : nb);
     if (grid && (write || out_index)) hipLaunchKernelGGL(ic_build_kernel, dim3(grid), dim3(kIBlock), 0, s, A);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "pkt_icmp_err_batch launch");
-    return PKT_SUCCESS;
-}
-
-// The outcome of the last ic_queue (the stream has passed it).
-int ic_finish(pkt_ctx_t* ctx, uint64_t* bytes_out_total, uint64_t* n_out) {
-    const IcmpScratch& ic = ctx->ic;
-    if (bytes_out_total) *bytes_out_total = ic.ctl[0];
-    if (n_out) *n_out = ic.ctl[1];
-    if (ic.ctl[2]) return ic_refuse(ctx, "the outputs do not fit out_cap / dst_len (the totals are the capacity needed)");
     return PKT_SUCCESS;
 }
 
@@ -511,15 +398,11 @@ int pkt_icmp_err_batch(pkt_ctx_t* ctx, const pkt_batch_t* batch, const pkt_chain
                        uint32_t* out_index, uint8_t* dst, uint64_t dst_len, uint64_t out_cap, uint64_t* out_off,
                        uint32_t* out_len, uint32_t* src_index, const pkt_chain_t* out_chain, uint64_t* hits,
                        uint64_t* bytes_out_total, uint64_t* n_out, void* stream) {
-    if (bytes_out_total) *bytes_out_total = 0;
-    if (n_out) *n_out = 0;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int rc = ic_queue(ctx, batch, chain, which_ip, flags, cfg, code, code_all, map, mtu, mtu_all, select, status,
-                            out_index, dst, dst_len, out_cap, out_off, out_len, src_index, out_chain, hits, s);
-    if (rc != PKT_SUCCESS) return rc;
-    const hipError_t e = hipStreamSynchronize(s);  // the one host wait, for the totals
-    if (e != hipSuccess) return hip_fail(ctx, e, "pkt_icmp_err_batch");
-    return ic_finish(ctx, bytes_out_total, n_out);
+    const auto queue = [&](hipStream_t s) {
+        return ic_queue(ctx, batch, chain, which_ip, flags, cfg, code, code_all, map, mtu, mtu_all, select, status, out_index,
+                        dst, dst_len, out_cap, out_off, out_len, src_index, out_chain, hits, s);
+    };
+    return pktgpu_out_batch(ctx, kIcmpEntry, queue, stream, bytes_out_total, n_out);
 }
 
 int pkt_icmp_err_batch_async(pkt_ctx_t* ctx, const pkt_batch_t* batch, const pkt_chain_t* chain, uint32_t which_ip,
@@ -528,23 +411,15 @@ int pkt_icmp_err_batch_async(pkt_ctx_t* ctx, const pkt_batch_t* batch, const pkt
                              uint8_t* status, uint32_t* out_index, uint8_t* dst, uint64_t dst_len, uint64_t out_cap,
                              uint64_t* out_off, uint32_t* out_len, uint32_t* src_index, const pkt_chain_t* out_chain,
                              uint64_t* hits, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int rc = ic_queue(ctx, batch, chain, which_ip, flags, cfg, code, code_all, map, mtu, mtu_all, select, status,
-                            out_index, dst, dst_len, out_cap, out_off, out_len, src_index, out_chain, hits, s);
-    if (rc != PKT_SUCCESS) return rc;
-    ctx->ic.mark(s);
-    return PKT_SUCCESS;
+    const auto queue = [&](hipStream_t s) {
+        return ic_queue(ctx, batch, chain, which_ip, flags, cfg, code, code_all, map, mtu, mtu_all, select, status, out_index,
+                        dst, dst_len, out_cap, out_off, out_len, src_index, out_chain, hits, s);
+    };
+    return pktgpu_out_batch_async(ctx, kIcmpEntry, queue, stream);
 }
 
 int pkt_icmp_err_result(pkt_ctx_t* ctx, uint64_t* bytes_out_total, uint64_t* n_out) {
-    if (bytes_out_total) *bytes_out_total = 0;
-    if (n_out) *n_out = 0;
-    if (!ctx) return PKT_ERR_INVALID_ARG;
-    IcmpScratch& ic = ctx->ic;
-    if (!ic.pending) return fail(ctx, PKT_ERR_INVALID_ARG, "pkt_icmp_err_result: no call queued on this ctx");
-    const hipError_t e = ic.take();
-    if (e != hipSuccess) return hip_fail(ctx, e, "pkt_icmp_err_result");
-    return ic_finish(ctx, bytes_out_total, n_out);
+    return pktgpu_out_result(ctx, kIcmpEntry, bytes_out_total, n_out);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 
 #include "pktgpu_batch.hpp"
 #include "pktgpu_frag.hpp"
+#include "pktgpu_outbatch.hpp"
 
 static_assert(sizeof(pkt_icmp_cfg_t) == 28, "icmp ABI struct");
 
@@ -223,7 +224,7 @@ PKT_HD uint32_t icmp_csum(const IcmpPlan& p, uint32_t part, uint32_t quote) {
     return !p.v4 && c == 0 ? 0xFFFFu : c;
 }
 
-// ---- the refusals both entry points share: the text (after "pkt_icmp_err_batch: "), or nullptr.
+// ---- the refusals both entry points share: the text (after "pkt_icmp_err_batch: "), or nullptr; the contract's own last.
 // device: pkt_icmp_err_batch (the slab's alignment rule); else pkt_icmp_err_host.
 inline const char* icmp_call_error(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
                                    const pkt_icmp_cfg_t* cfg, uint32_t code_all, const uint16_t* mtu, uint32_t mtu_all,
@@ -243,18 +244,6 @@ inline const char* icmp_call_error(const pkt_batch_t* b, const pkt_chain_t* chai
     if (code_all > 255u) return "code_all above 255";
     if (mtu_all > 65535u) return "mtu_all above 65535";
     if ((uintptr_t)mtu & 1) return "mtu not 2-byte aligned";
-    if ((uintptr_t)hits & 7) return "hits not 8-byte aligned";
-    if ((uintptr_t)dst & 15) return "dst not 16-byte aligned";
-    if ((uintptr_t)out_off & 7) return "out_off not 8-byte aligned";
-    if (!(flags & PKT_ICMPE_NO_WRITE)) {
-        if (!dst || !out_off || !out_len) return "null dst, out_off or out_len without PKT_ICMPE_NO_WRITE";
-        if (out_cap == 0 || out_cap >= (1ull << 32)) return "out_cap is 0 or >= 2^32";
-    }
-    if (b->n) {
-        if (!chain->n_hdrs || !chain->hdr_type || !chain->hdr_off) return "null chain column";
-        const char* msg = device ? batch_slab16_error(b) : batch_null_slab(b) ? "null slab" : nullptr;
-        if (msg) return msg;
-        return batch_index_error(b);
-    }
-    return nullptr;
+    return out_call_error(b, chain, flags & PKT_ICMPE_NO_WRITE, "null dst, out_off or out_len without PKT_ICMPE_NO_WRITE", dst,
+                          out_cap, out_off, out_len, hits, device);
 }

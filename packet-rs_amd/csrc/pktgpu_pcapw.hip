@@ -54,24 +54,6 @@ __device__ __forceinline__ uint64_t w_contrib(const WSrc& a, uint64_t i) {
     return (uint64_t)(16u + w_incl(a, pkt_len(a.b, i, pkt_off(a.b, i)))) | 1ull << 32;
 }
 
-// Exclusive prefix of v over the block's threads; total = the block's sum.  (s_w: one word per wave.)
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* s_w, uint64_t& total) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint64_t x = wave_incl_scan(v, lane);
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    uint64_t base = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kPwWaves; k++) {
-        const uint64_t t = s_w[k];
-        base += k < wv ? t : 0;
-        total += t;
-    }
-    __syncthreads();  // s_w may be written again
-    return base + x - v;
-}
-
 // a tile's sums: at most 1024 * 65551 bytes and 1024 records, so both halves of the packed word hold
 __global__ __launch_bounds__(kPwBlock) void pw_reduce_kernel(WSrc a, uint64_t* __restrict__ blk_bytes,
                                                              uint32_t* __restrict__ blk_cnt) {
@@ -81,7 +63,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_reduce_kernel(WSrc a, uint64_t* _
 #pragma unroll
     for (uint32_t j = 0; j < kPwPer; j++) v += w_contrib(a, i0 + j);
     uint64_t total;
-    (void)block_excl_scan(v, s_w, total);
+    (void)block_excl_scan<kPwWaves>(v, s_w, total);
     if (threadIdx.x == 0) {
         blk_bytes[blockIdx.x] = total & 0xFFFFFFFFull;
         blk_cnt[blockIdx.x] = (uint32_t)(total >> 32);
@@ -107,8 +89,8 @@ __global__ __launch_bounds__(kPwBlock) void pw_scan_kernel(uint64_t* __restrict_
             sc += c[j];
         }
         uint64_t tb, tc;
-        uint64_t eb = cb + block_excl_scan(sb, s_w, tb);
-        uint64_t ec = cc + block_excl_scan(sc, s_w, tc);
+        uint64_t eb = cb + block_excl_scan<kPwWaves>(sb, s_w, tb);
+        uint64_t ec = cc + block_excl_scan<kPwWaves>(sc, s_w, tc);
 #pragma unroll
         for (uint32_t j = 0; j < kPwScanPer; j++) {
             if (i0 + j < nb) {
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_emit_kernel(WSrc a, const uint64_
         v += c[j];
     }
     uint64_t total;
-    const uint64_t ex = block_excl_scan(v, s_w, total);
+    const uint64_t ex = block_excl_scan<kPwWaves>(v, s_w, total);
     const uint64_t kbase = blk_cnt[blockIdx.x];
     uint64_t pos = blk_bytes[blockIdx.x] + (ex & 0xFFFFFFFFull);
     uint32_t lk = (uint32_t)(ex >> 32);  // the record's place among the tile's
@@ -320,8 +302,6 @@ __global__ __launch_bounds__(kPwBlock) void pw_copy_kernel(WSrc a, const uint64_
     }
 }
 
-uint64_t round16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
-
 // The four launches, queued on s.  The totals arrive in ctx->pw.ctl once the stream has passed them.
 int pw_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const uint8_t* select, uint32_t snaplen, uint32_t tv_sec,
              uint32_t tv_usec, const uint32_t* ts_sec, const uint32_t* ts_usec, uint8_t* dst, uint64_t dst_len,
@@ -353,13 +333,7 @@ int pw_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const uint8_t* select, uint32
     const uint64_t o_bytes = 64, o_cnt = o_bytes + round16(8ull * nb), o_first = o_cnt + round16(4ull * nb);
     const uint64_t o_koff = o_first + round16(4 * nwin), o_ksrc = o_koff + (rec_offsets ? 0 : round16(8 * n));
     const uint64_t need = o_ksrc + (src_index ? 0 : round16(4 * n));
-    if (need > pw.bytes) {
-        if (pw.buf) (void)hipFree(pw.buf);  // (waits for the device: no earlier write still uses it)
-        pw.buf = nullptr;
-        pw.bytes = 0;
-        if ((e = hipMalloc(&pw.buf, need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pcap write)");
-        pw.bytes = need;
-    }
+    if ((e = pw.reserve(need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pcap write)");
     if ((e = pw.ensure(64)) != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (pcap write)");
     char* p = static_cast<char*>(pw.buf);
     uint64_t* tot = reinterpret_cast<uint64_t*>(p);

@@ -19,7 +19,8 @@
 //   rs_count_kernel     the verdict (reasm_verdict) from the datagram's words, the final status, each packet's
 //                       output length (WHOLE, or the owner of a JOINED datagram; else 0), the tile's (outputs,
 //                       rounded bytes), and the per-status counts merged in LDS and added once per block;
-//   rs_scan_kernel      one block: the exclusive prefix of the tile sums, the totals and the overflow verdict;
+//   out_scan_kernel     (pktgpu_outbatch.hip, shared with frag and icmp) one block: the exclusive prefix of the tile
+//                       sums, the totals and the overflow verdict;
 //   rs_emit_kernel      per tile: a block scan gives each emitting packet its output index and offset; it writes the
 //                       output's row (out_off, out_len, src_index, nfrag, out_chain) and where the output lies (ROut,
 //                       by representative) for the members;
@@ -43,7 +44,6 @@ namespace {
 
 constexpr uint32_t kRBlock = 256;
 constexpr uint32_t kRWaves = kRBlock / 64;
-constexpr uint32_t kRScanPer = 16;       // tile sums per thread and round of the scan
 constexpr uint32_t kCountBlocks = 1280;  // the counting launch's grid cap (pktgpu_frag.hip's)
 constexpr uint32_t kNoHdr = 0x7FFFFF00u;  // a staged packet without a header to rebuild
 
@@ -115,24 +115,6 @@ __device__ __forceinline__ Member rec_unpack(uint4 v) {
 
 __device__ __forceinline__ bool emits_whole(uint32_t st, uint32_t flags) {
     return st == PKT_REASM_WHOLE && !(flags & PKT_REASM_ONLY_JOINED);
-}
-
-// Exclusive prefix of v over the block's threads; total = the block's sum.  (s_w: one word per wave.)
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* s_w, uint64_t& total) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint64_t x = wave_incl_scan(v, lane);
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    uint64_t base = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kRWaves; k++) {
-        const uint64_t t = s_w[k];
-        base += k < wv ? t : 0;
-        total += t;
-    }
-    __syncthreads();  // s_w may be written again
-    return base + x - v;
 }
 
 // the slab bytes [S, S + 4 * W), W = 3 or 5 dwords, which lie inside a packet: the aligned chunk of S and the next
@@ -260,11 +242,8 @@ __global__ __launch_bounds__(kRBlock) void rs_link_kernel(RParams P) {
 __global__ __launch_bounds__(kRBlock) void rs_count_kernel(RParams P) {
     __shared__ uint32_t s_hits[PKT_REASM_STATUS_COUNT];
     __shared__ uint64_t s_w[kRWaves];
-    const uint32_t t = threadIdx.x, lane = t & 63u;
-    if (P.hits) {
-        if (t < PKT_REASM_STATUS_COUNT) s_hits[t] = 0;
-        __syncthreads();
-    }
+    const uint32_t t = threadIdx.x;
+    if (P.hits) hits_zero<PKT_REASM_STATUS_COUNT>(s_hits, t);
     const uint32_t ntiles = (uint32_t)((P.n + kRBlock - 1) / kRBlock);
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // uniform
         const uint64_t i = (uint64_t)tile * kRBlock + t;
@@ -285,66 +264,15 @@ __global__ __launch_bounds__(kRBlock) void rs_count_kernel(RParams P) {
             P.olen[i] = ol;
         }
         uint64_t tc, tb;
-        (void)block_excl_scan(ol ? 1u : 0u, s_w, tc);
-        (void)block_excl_scan(frag_round16(ol), s_w, tb);
+        (void)block_excl_scan<kRWaves>(ol ? 1u : 0u, s_w, tc);
+        (void)block_excl_scan<kRWaves>(out_round16(ol), s_w, tb);
         if (t == 0) {
             P.blk_cnt[tile] = tc;
             P.blk_bytes[tile] = tb;
         }
-        if (P.hits) {
-#pragma unroll
-            for (uint32_t s = 0; s < PKT_REASM_STATUS_COUNT; s++) {
-                const uint64_t b = __ballot(act && st == s);
-                if (lane == 0 && b) atomicAdd(&s_hits[s], (uint32_t)__popcll((unsigned long long)b));
-            }
-        }
+        if (P.hits) hits_add<PKT_REASM_STATUS_COUNT>(s_hits, t, act, st);
     }
-    if (!P.hits) return;
-    __syncthreads();
-    if (t < PKT_REASM_STATUS_COUNT) {
-        const uint32_t h = s_hits[t];
-        if (h) __hip_atomic_fetch_add(P.hits + t, (uint64_t)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// tot: [total rounded bytes, outputs, overflow] on the device; host: the same three words in pinned memory
-__global__ __launch_bounds__(kRBlock) void rs_scan_kernel(uint64_t* __restrict__ blk_bytes, uint64_t* __restrict__ blk_cnt,
-                                                          uint32_t nb, uint32_t no_write, uint64_t out_cap,
-                                                          uint64_t dst_len, uint64_t* __restrict__ tot,
-                                                          uint64_t* __restrict__ host) {
-    __shared__ uint64_t s_w[kRWaves];
-    uint64_t cb = 0, cc = 0;
-    for (uint64_t base = 0; base < nb; base += (uint64_t)kRBlock * kRScanPer) {
-        const uint64_t i0 = base + (uint64_t)threadIdx.x * kRScanPer;
-        uint64_t b[kRScanPer], c[kRScanPer], sb = 0, sc = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kRScanPer; j++) {
-            const bool in = i0 + j < nb;
-            b[j] = in ? blk_bytes[i0 + j] : 0;
-            c[j] = in ? blk_cnt[i0 + j] : 0;
-            sb += b[j];
-            sc += c[j];
-        }
-        uint64_t tb, tc;
-        uint64_t eb = cb + block_excl_scan(sb, s_w, tb);
-        uint64_t ec = cc + block_excl_scan(sc, s_w, tc);
-#pragma unroll
-        for (uint32_t j = 0; j < kRScanPer; j++) {
-            if (i0 + j < nb) {
-                blk_bytes[i0 + j] = eb;
-                blk_cnt[i0 + j] = ec;
-            }
-            eb += b[j];
-            ec += c[j];
-        }
-        cb += tb;
-        cc += tc;
-    }
-    if (threadIdx.x == 0) {
-        const uint64_t over = !no_write && frag_overflow(cc, cb, out_cap, dst_len) ? 1u : 0u;
-        tot[0] = cb, tot[1] = cc, tot[2] = over;
-        host[0] = cb, host[1] = cc, host[2] = over;
-    }
+    if (P.hits) hits_flush<PKT_REASM_STATUS_COUNT>(s_hits, t, P.hits);
 }
 
 __global__ __launch_bounds__(kRBlock) void rs_emit_kernel(RParams P) {
@@ -353,8 +281,8 @@ __global__ __launch_bounds__(kRBlock) void rs_emit_kernel(RParams P) {
     const bool act = i < P.n;
     const uint32_t ol = act ? P.olen[i] : 0u;
     uint64_t tc, tb;
-    const uint64_t q = P.blk_cnt[blockIdx.x] + block_excl_scan(ol ? 1u : 0u, s_w, tc);
-    const uint64_t o = P.blk_bytes[blockIdx.x] + block_excl_scan(frag_round16(ol), s_w, tb);
+    const uint64_t q = P.blk_cnt[blockIdx.x] + block_excl_scan<kRWaves>(ol ? 1u : 0u, s_w, tc);
+    const uint64_t o = P.blk_bytes[blockIdx.x] + block_excl_scan<kRWaves>(out_round16(ol), s_w, tb);
     if (!ol) return;
     // an emitting packet is WHOLE, or the owner of a JOINED datagram
     uint64_t rows_of = i, g = i;
@@ -379,18 +307,6 @@ __global__ __launch_bounds__(kRBlock) void rs_emit_kernel(RParams P) {
         if (P.oc_ty) P.oc_ty[(uint64_t)k * P.out_cap + q] = P.hdr_type[(uint64_t)k * P.n + rows_of];
         if (P.oc_of) P.oc_of[(uint64_t)k * P.out_cap + q] = P.hdr_off[(uint64_t)k * P.n + rows_of];
     }
-}
-
-// the 16 slab bytes from `pos` on, pos < slab_len: the second aligned chunk is clamped to the slab's last one (what
-// it then gives lies past the slab, so past every packet: the caller masks it off)
-__device__ __forceinline__ Le128 load16(const uint8_t* slab, uint64_t pos, uint64_t last16) {
-    const uint64_t A = pos & ~(uint64_t)15;
-    const uint64_t B = A + 16 > last16 ? last16 : A + 16;
-    const uint4 v0 = *reinterpret_cast<const uint4*>(slab + A);
-    const uint4 v1 = *reinterpret_cast<const uint4*>(slab + B);
-    uint32_t o[4];
-    take16(v0, v1, (uint32_t)pos & 15u, o);
-    return Le128{(uint64_t)o[0] | (uint64_t)o[1] << 32, (uint64_t)o[2] | (uint64_t)o[3] << 32};
 }
 
 __global__ __launch_bounds__(kRBlock) void rs_copy_kernel(RParams P) {
@@ -443,7 +359,7 @@ __global__ __launch_bounds__(kRBlock) void rs_copy_kernel(RParams P) {
         s_src[wv][lane] = S0 - lo;  // S0 >= 20 where lo > 0: a member's payload lies behind its IP header
         s_lo[wv][lane] = lo;
         s_dend[wv][lane] = dend;
-        s_hend[wv][lane] = last ? frag_round16(dend) : dend;
+        s_hend[wv][lane] = last ? out_round16(dend) : dend;
         s_ipo[wv][lane] = ipo;
         s_h[wv][0][lane] = o[0], s_h[wv][1][lane] = o[1], s_h[wv][2][lane] = o[2];
         chunks = (dend + 15u) >> 4;  // at most 4096
@@ -454,7 +370,7 @@ __global__ __launch_bounds__(kRBlock) void rs_copy_kernel(RParams P) {
     wave_sync();
     const uint32_t total = s_pre[wv][64];  // at most 64 * 4096
     const FlatWalk w = flat_walk(chunks);
-    const uint64_t last16 = P.src.slab_len ? ((P.src.slab_len + 15) & ~(uint64_t)15) - 16 : 0;
+    const uint64_t last16 = slab_last16(P.src);
     for (uint32_t f = lane; f < total; f += 64) {
         const FlatAt at = locate(w, s_pre[wv], f);
         const uint32_t s = at.p, B0 = 16u * at.k;  // the chunk's first byte, counted from the packet's aligned start
@@ -503,12 +419,7 @@ __global__ __launch_bounds__(kRBlock) void rs_index_kernel(RParams P) {
     P.out_index[i] = q;
 }
 
-uint64_t round16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
-
-int rs_refuse(pkt_ctx* ctx, const char* msg) {
-    if (ctx) ctx->err = std::string("pkt_reasm_batch: ") + msg;
-    return PKT_ERR_INVALID_ARG;
-}
+constexpr OutEntry kReasmEntry{&pkt_ctx::rs, "pkt_reasm_batch", "pkt_reasm_result"};
 
 // The launches, queued on s.  The totals and the verdict arrive in ctx->rs.ctl once the stream has passed them.
 int rs_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
@@ -517,9 +428,10 @@ int rs_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
              uint64_t* hits, hipStream_t s) {
     if (!ctx) return PKT_ERR_INVALID_ARG;
     if (const char* msg = reasm_call_error(b, chain, which_ip, flags, dst, out_cap, out_off, out_len, hits, true))
-        return rs_refuse(ctx, msg);
-    ReasmScratch& rs = ctx->rs;
-    if (rs.pending) return rs_refuse(ctx, "a queued call's result has not been taken on this ctx (pkt_reasm_result)");
+        return pktgpu_out_refuse(ctx, kReasmEntry, msg);
+    OutScratch& rs = ctx->rs;
+    if (rs.pending)
+        return pktgpu_out_refuse(ctx, kReasmEntry, "a queued call's result has not been taken on this ctx (pkt_reasm_result)");
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     const bool write = !(flags & PKT_REASM_NO_WRITE);
@@ -533,13 +445,7 @@ int rs_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
     const uint64_t o_gout = o_rec + 16 * n, o_aux = o_gout + 16 * n, o_grp = o_aux + round16(8 * n);
     const uint64_t o_olen = o_grp + round16(4 * n), o_st = o_olen + round16(4 * n), o_acc = o_st + round16(n);
     const uint64_t o_tab2 = o_acc + 32 * n, o_tab1 = o_tab2 + 8 * slots, need = o_tab1 + 4 * slots;
-    if (need > rs.bytes) {
-        if (rs.buf) (void)hipFree(rs.buf);  // (waits for the device: no earlier call still uses it)
-        rs.buf = nullptr;
-        rs.bytes = 0;
-        if ((e = hipMalloc(&rs.buf, need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pkt_reasm_batch)");
-        rs.bytes = need;
-    }
+    if ((e = rs.reserve(need)) != hipSuccess) return hip_fail(ctx, e, "hipMalloc (pkt_reasm_batch)");
     if ((e = rs.ensure(64)) != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc (pkt_reasm_batch)");
     char* p = static_cast<char*>(rs.buf);
     RParams P{};
@@ -574,11 +480,8 @@ int rs_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
         P.out_len = out_len;
         P.src_index = src_index;
         P.nfrag = nfrag;
-        if (out_chain) {
-            P.oc_nh = const_cast<uint8_t*>(out_chain->n_hdrs);
-            P.oc_ty = const_cast<uint8_t*>(out_chain->hdr_type);
-            P.oc_of = const_cast<uint16_t*>(out_chain->hdr_off);
-        }
+        const OutChainCols oc = out_chain_cols(out_chain);
+        P.oc_nh = oc.nh, P.oc_ty = oc.ty, P.oc_of = oc.of;
     }
     rs.ctl[0] = rs.ctl[1] = rs.ctl[2] = 0;
     const dim3 blk(kRBlock);
@@ -590,8 +493,7 @@ int rs_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
         hipLaunchKernelGGL(rs_link_kernel, dim3(nb), blk, 0, s, P);
         hipLaunchKernelGGL(rs_count_kernel, dim3(hits && nb > kCountBlocks ? kCountBlocks : nb), blk, 0, s, P);
     }
-    hipLaunchKernelGGL(rs_scan_kernel, dim3(1), blk, 0, s, P.blk_bytes, P.blk_cnt, nb, write ? 0u : 1u, out_cap, dst_len, P.tot,
-                       rs.ctl_dev);
+    pktgpu_out_scan_launch(P.blk_bytes, P.blk_cnt, nb, !write, out_cap, dst_len, P.tot, rs.ctl_dev, s);
     if (nb && (write || out_index)) hipLaunchKernelGGL(rs_emit_kernel, dim3(nb), blk, 0, s, P);
     if (write) {
         const uint64_t lanes = n > out_cap ? n : out_cap;
@@ -599,15 +501,6 @@ int rs_queue(pkt_ctx_t* ctx, const pkt_batch_t* b, const pkt_chain_t* chain, uin
     }
     if (nb && out_index) hipLaunchKernelGGL(rs_index_kernel, dim3(nb), blk, 0, s, P);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "pkt_reasm_batch launch");
-    return PKT_SUCCESS;
-}
-
-// The outcome of the last rs_queue (the stream has passed it).
-int rs_finish(pkt_ctx_t* ctx, uint64_t* bytes_out_total, uint64_t* n_out) {
-    const ReasmScratch& rs = ctx->rs;
-    if (bytes_out_total) *bytes_out_total = rs.ctl[0];
-    if (n_out) *n_out = rs.ctl[1];
-    if (rs.ctl[2]) return rs_refuse(ctx, "the outputs do not fit out_cap / dst_len (the totals are the capacity needed)");
     return PKT_SUCCESS;
 }
 
@@ -619,38 +512,26 @@ int pkt_reasm_batch(pkt_ctx_t* ctx, const pkt_batch_t* batch, const pkt_chain_t*
                     const uint8_t* select, uint8_t* status, uint32_t* out_index, uint8_t* dst, uint64_t dst_len,
                     uint64_t out_cap, uint64_t* out_off, uint32_t* out_len, uint32_t* src_index, uint32_t* nfrag,
                     const pkt_chain_t* out_chain, uint64_t* hits, uint64_t* bytes_out_total, uint64_t* n_out, void* stream) {
-    if (bytes_out_total) *bytes_out_total = 0;
-    if (n_out) *n_out = 0;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int rc = rs_queue(ctx, batch, chain, which_ip, flags, select, status, out_index, dst, dst_len, out_cap, out_off,
-                            out_len, src_index, nfrag, out_chain, hits, s);
-    if (rc != PKT_SUCCESS) return rc;
-    const hipError_t e = hipStreamSynchronize(s);  // the one host wait, for the totals
-    if (e != hipSuccess) return hip_fail(ctx, e, "pkt_reasm_batch");
-    return rs_finish(ctx, bytes_out_total, n_out);
+    const auto queue = [&](hipStream_t s) {
+        return rs_queue(ctx, batch, chain, which_ip, flags, select, status, out_index, dst, dst_len, out_cap, out_off, out_len,
+                        src_index, nfrag, out_chain, hits, s);
+    };
+    return pktgpu_out_batch(ctx, kReasmEntry, queue, stream, bytes_out_total, n_out);
 }
 
 int pkt_reasm_batch_async(pkt_ctx_t* ctx, const pkt_batch_t* batch, const pkt_chain_t* chain, uint32_t which_ip,
                           uint32_t flags, const uint8_t* select, uint8_t* status, uint32_t* out_index, uint8_t* dst,
                           uint64_t dst_len, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len, uint32_t* src_index,
                           uint32_t* nfrag, const pkt_chain_t* out_chain, uint64_t* hits, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int rc = rs_queue(ctx, batch, chain, which_ip, flags, select, status, out_index, dst, dst_len, out_cap, out_off,
-                            out_len, src_index, nfrag, out_chain, hits, s);
-    if (rc != PKT_SUCCESS) return rc;
-    ctx->rs.mark(s);
-    return PKT_SUCCESS;
+    const auto queue = [&](hipStream_t s) {
+        return rs_queue(ctx, batch, chain, which_ip, flags, select, status, out_index, dst, dst_len, out_cap, out_off, out_len,
+                        src_index, nfrag, out_chain, hits, s);
+    };
+    return pktgpu_out_batch_async(ctx, kReasmEntry, queue, stream);
 }
 
 int pkt_reasm_result(pkt_ctx_t* ctx, uint64_t* bytes_out_total, uint64_t* n_out) {
-    if (bytes_out_total) *bytes_out_total = 0;
-    if (n_out) *n_out = 0;
-    if (!ctx) return PKT_ERR_INVALID_ARG;
-    ReasmScratch& rs = ctx->rs;
-    if (!rs.pending) return fail(ctx, PKT_ERR_INVALID_ARG, "pkt_reasm_result: no call queued on this ctx");
-    const hipError_t e = rs.take();
-    if (e != hipSuccess) return hip_fail(ctx, e, "pkt_reasm_result");
-    return rs_finish(ctx, bytes_out_total, n_out);
+    return pktgpu_out_result(ctx, kReasmEntry, bytes_out_total, n_out);
 }
 
 }  // extern "C"

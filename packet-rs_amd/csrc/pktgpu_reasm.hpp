@@ -10,6 +10,7 @@
 #include "pktgpu_batch.hpp"
 #include "pktgpu_flow.hpp"
 #include "pktgpu_frag.hpp"
+#include "pktgpu_outbatch.hpp"
 
 constexpr uint32_t kReasmFlags = PKT_REASM_ONLY_JOINED | PKT_REASM_NO_WRITE;
 
@@ -90,7 +91,7 @@ PKT_HD void reasm_header(uint32_t E, const uint32_t h[3], uint32_t o[3]) {
     o[2] = (h[2] & 0xFFFFu) | fwd_be16(hc2) << 16;
 }
 
-// ---- the refusals both entry points share: the text (after "pkt_reasm_batch: "), or nullptr.
+// ---- the refusals both entry points share: the text (after "pkt_reasm_batch: "), or nullptr; the contract's own last.
 // device: pkt_reasm_batch (the slab's alignment rule); else pkt_reasm_host.
 inline const char* reasm_call_error(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
                                     const uint8_t* dst, uint64_t out_cap, const uint64_t* out_off, const uint32_t* out_len,
@@ -99,18 +100,6 @@ inline const char* reasm_call_error(const pkt_batch_t* b, const pkt_chain_t* cha
     if (b->n >= (1ull << 32)) return "n >= 2^32";
     if (flags & ~kReasmFlags) return "unknown flag bits";
     if (which_ip >= PKT_MAX_HDRS && which_ip != PKT_FLOW_LAST) return "which_ip is neither below 16 nor PKT_FLOW_LAST";
-    if ((uintptr_t)hits & 7) return "hits not 8-byte aligned";
-    if ((uintptr_t)dst & 15) return "dst not 16-byte aligned";
-    if ((uintptr_t)out_off & 7) return "out_off not 8-byte aligned";
-    if (!(flags & PKT_REASM_NO_WRITE)) {
-        if (!dst || !out_off || !out_len) return "null dst, out_off or out_len without PKT_REASM_NO_WRITE";
-        if (out_cap == 0 || out_cap >= (1ull << 32)) return "out_cap is 0 or >= 2^32";
-    }
-    if (b->n) {
-        if (!chain->n_hdrs || !chain->hdr_type || !chain->hdr_off) return "null chain column";
-        const char* msg = device ? batch_slab16_error(b) : batch_null_slab(b) ? "null slab" : nullptr;
-        if (msg) return msg;
-        return batch_index_error(b);
-    }
-    return nullptr;
+    return out_call_error(b, chain, flags & PKT_REASM_NO_WRITE, "null dst, out_off or out_len without PKT_REASM_NO_WRITE", dst,
+                          out_cap, out_off, out_len, hits, device);
 }

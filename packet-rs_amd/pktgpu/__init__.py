@@ -1841,28 +1841,30 @@ class Forwarder:
 FRAG_NONE, FRAG_ONLY_SPLIT, FRAG_NO_WRITE = schema.FRAG_NONE, schema.FRAG_ONLY_SPLIT, schema.FRAG_NO_WRITE
 
 
-class FragResult:
-    """What Parser.fragment gives.  Per source packet: status (uint8: pktgpu.FRAG_FITS / _SPLIT / _SKIPPED / _NO_IP /
-    _SPAN / _IPV6 / _BAD_HDR / _TRUNC / _DF / _MTU), nfrag, first (uint32; FRAG_NONE where nfrag is 0).  The totals:
-    n_out, bytes_out.  Unless plan_only, per output (arrays of out_cap entries, empty past n_out): slab, offsets,
-    lens, src_index, frag_index and out_chain ({"n_hdrs", "hdr_type", "hdr_off"}, slot-major over out_cap); batch()
-    is the output as the batch dict the other calls take.  hits: the per-status counters, if asked for."""
+class _Produced:
+    """What the results of Parser.fragment, .reassemble and .icmp_errors share (_produce fills them in)."""
+    slab = offsets = lens = src_index = out_chain = hits = None
 
     def __init__(self, **kw):
-        self.slab = self.offsets = self.lens = self.src_index = self.frag_index = self.out_chain = self.hits = None
         self.__dict__.update(kw)
 
     def batch(self):
         return dict(slab=self.slab, offsets=self.offsets, lens=self.lens)
 
 
-def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only, out_cap, dst_bytes, hits, host, stream):
+def _produce(parser, e, batch, chain, select, which_ip, flags, inputs, plan_only, out_cap, dst_bytes, hits, host, stream):
+    """The call sequence of the three entries that pack outputs into a second slab (pktgpu_outbatch.hpp's contract).
+    `e`: the entry (its C functions' stem, result class, status count, NO_WRITE flag, per-packet outputs and its own
+    per-output column, if any); `inputs(per_packet)`: the entry's own C arguments, between flags and select, where
+    per_packet(v, dtype) turns a value for all packets or one per packet into the (array, scalar) argument pair."""
     from . import _lib
     L = _lib.load()
+    if hasattr(batch, "batch") and callable(batch.batch):
+        batch = batch.batch()
     if isinstance(batch, (tuple, list)):
         batch = dict(zip(("slab", "offsets", "lens"), batch))
     g = lambda k: batch.get(k)  # noqa: E731
-    nc = schema.FRAG_STATUS_COUNT
+    fn, nc, what = e["fn"], e["nc"], e["what"]
     if host:
         b, keep = _host_batch(_lib, batch)
         cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
@@ -1872,8 +1874,7 @@ def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only
         empty = lambda k, dt: np.zeros(k, dt)  # noqa: E731
         ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
         ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
-        if not np.isscalar(mtu):
-            mtu = np.ascontiguousarray(mtu, np.uint16)
+        column = lambda v, dt: np.ascontiguousarray(v, dt)  # noqa: E731
     else:
         torch = _torch()
         b = parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
@@ -1884,45 +1885,50 @@ def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only
         empty = lambda k, dt: torch.zeros(k, dtype=_tdtype(dt), device=dev)  # noqa: E731
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
         ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
-        if not isinstance(mtu, (int, np.integer)):
-            assert mtu.is_cuda and mtu.dtype == torch.uint16 and mtu.is_contiguous() and mtu.numel() >= b.n
-    per_pkt = not isinstance(mtu, (int, np.integer))
+
+        def column(v, dt):
+            assert v.is_cuda and v.dtype == _tdtype(dt) and v.is_contiguous() and v.numel() >= b.n
+            return v
+    held = []  # the per-packet inputs, alive until the calls are done
+
+    def per_packet(v, dt):
+        if isinstance(v, (int, np.integer)):
+            return None, int(v)
+        held.append(column(v, dt))
+        return ptr(held[-1]), 0
+
+    ins = inputs(per_packet)
     if hits is True:
         hits = empty(nc, np.uint64)
     if hits is not None and hits is not False:
-        assert ok(hits), f"fragment: hits is a contiguous uint64 [{nc}] array"
+        assert ok(hits), f"{what}: hits is a contiguous uint64 [{nc}] array"
     else:
         hits = None
-    n = b.n
-    res = FragResult(status=empty(n, np.uint8), nfrag=empty(n, np.uint32), first=empty(n, np.uint32), hits=hits)
-    flags = schema.FRAG_ONLY_SPLIT if only_split else 0
+    res = e["result"](hits=hits, **{k: empty(b.n, dt) for k, dt in e["per_packet"]})
+    extra = [e["extra"]] if e["extra"] else []
     tot, cnt = ctypes.c_uint64(0), ctypes.c_uint64(0)
 
     def call(fl, out, with_hits):
-        dst, cap = out.get("slab"), out.get("cap", 0)
+        dst = out.get("slab")
         oc = None
         if out:
             oc = _lib.PktChain(*[ptr(out["out_chain"][k]) for k in ("n_hdrs", "hdr_type", "hdr_off")])
-        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), fl, ptr(mtu) if per_pkt else None,
-                0 if per_pkt else int(mtu), ptr(select), ptr(res.status), ptr(res.nfrag), ptr(res.first),
-                dst.ctypes.data if host and dst is not None else dst.data_ptr() if dst is not None else None,
-                0 if dst is None else int(dst.size if host else dst.numel()), cap, ptr(out.get("offsets")), ptr(out.get("lens")),
-                ptr(out.get("src_index")), ptr(out.get("frag_index")), ctypes.byref(oc) if oc is not None else None,
-                ptr(hits) if with_hits else None, ctypes.byref(tot), ctypes.byref(cnt))
+        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), fl, *ins, ptr(select),
+                *[ptr(getattr(res, k)) for k, _ in e["per_packet"]],
+                ptr(dst), 0 if dst is None else int(dst.size if host else dst.numel()), out.get("cap", 0),
+                ptr(out.get("offsets")), ptr(out.get("lens")), ptr(out.get("src_index")), *[ptr(out.get(k)) for k, _ in extra],
+                ctypes.byref(oc) if oc is not None else None, ptr(hits) if with_hits else None, ctypes.byref(tot),
+                ctypes.byref(cnt))
         if host:
-            return L.pkt_frag_host(*args)
-        return L.pkt_frag_batch(parser._ctx, *args, parser._stream(stream))
-
-    def done(rc, what):
-        if rc == 0:
-            return
-        if host:
-            raise ValueError(f"pkt_frag_host failed ({rc}); it needs {cnt.value} outputs and {tot.value} bytes")
-        parser._check(rc, what)
+            rc = getattr(L, fn + "_host")(*args)
+            if rc != 0:
+                raise ValueError(f"{fn}_host failed ({rc}); it needs {cnt.value} outputs and {tot.value} bytes")
+        else:
+            parser._check(getattr(L, fn + "_batch")(parser._ctx, *args, parser._stream(stream)), fn + "_batch")
 
     sized = out_cap is not None and dst_bytes is not None
     if plan_only or not sized:
-        done(call(flags | schema.FRAG_NO_WRITE, {}, plan_only), "pkt_frag_batch")
+        call(flags | e["no_write"], {}, plan_only)
         if plan_only:
             res.n_out, res.bytes_out = cnt.value, tot.value
             return res
@@ -1930,13 +1936,31 @@ def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only
         dst_bytes = tot.value if dst_bytes is None else dst_bytes
     cap = max(1, int(out_cap))
     out = dict(slab=empty(max(16, int(dst_bytes)), np.uint8), cap=cap, offsets=empty(cap, np.uint64),
-               lens=empty(cap, np.uint32), src_index=empty(cap, np.uint32), frag_index=empty(cap, np.uint16),
+               lens=empty(cap, np.uint32), src_index=empty(cap, np.uint32), **{k: empty(cap, dt) for k, dt in extra},
                out_chain=dict(n_hdrs=empty(cap, np.uint8), hdr_type=empty((schema.MAX_HDRS, cap), np.uint8),
                               hdr_off=empty((schema.MAX_HDRS, cap), np.uint16)))
-    done(call(flags, out, True), "pkt_frag_batch")
+    call(flags, out, True)
     out.pop("cap")
     res.__dict__.update(out, n_out=cnt.value, bytes_out=tot.value)
     return res
+
+
+class FragResult(_Produced):
+    """What Parser.fragment gives.  Per source packet: status (uint8: pktgpu.FRAG_FITS / _SPLIT / _SKIPPED / _NO_IP /
+    _SPAN / _IPV6 / _BAD_HDR / _TRUNC / _DF / _MTU), nfrag, first (uint32; FRAG_NONE where nfrag is 0).  The totals:
+    n_out, bytes_out.  Unless plan_only, per output (arrays of out_cap entries, empty past n_out): slab, offsets,
+    lens, src_index, frag_index and out_chain ({"n_hdrs", "hdr_type", "hdr_off"}, slot-major over out_cap); batch()
+    is the output as the batch dict the other calls take.  hits: the per-status counters, if asked for."""
+    frag_index = None
+
+
+_FRAG = dict(what="fragment", fn="pkt_frag", result=FragResult, nc=schema.FRAG_STATUS_COUNT, no_write=schema.FRAG_NO_WRITE,
+             per_packet=(("status", np.uint8), ("nfrag", np.uint32), ("first", np.uint32)), extra=("frag_index", np.uint16))
+
+
+def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only, out_cap, dst_bytes, hits, host, stream):
+    return _produce(parser, _FRAG, batch, chain, select, which_ip, schema.FRAG_ONLY_SPLIT if only_split else 0,
+                    lambda per_packet: per_packet(mtu, np.uint16), plan_only, out_cap, dst_bytes, hits, host, stream)
 
 
 (ICMPE_SENT, ICMPE_SKIPPED, ICMPE_BAD_REASON, ICMPE_NO_IP, ICMPE_SPAN, ICMPE_NO_ETHER, ICMPE_NO_SRC, ICMPE_BAD_HDR,
@@ -1944,20 +1968,13 @@ def _fragment(parser, batch, chain, mtu, select, which_ip, only_split, plan_only
 ICMPE_NONE, ICMPE_NO_WRITE = schema.ICMPE_NONE, schema.ICMPE_NO_WRITE
 
 
-class IcmpErrResult:
+class IcmpErrResult(_Produced):
     """What Parser.icmp_errors gives.  Per source packet: status (uint8: pktgpu.ICMPE_SENT / _SKIPPED / _BAD_REASON /
     _NO_IP / _SPAN / _NO_ETHER / _NO_SRC / _BAD_HDR / _FRAGMENT / _BAD_SRC / _MCAST / _ICMP_ERR) and out_index (uint32:
     the packet's output, ICMPE_NONE where there is none).  The totals: n_out, bytes_out.  Unless plan_only, per output
     (arrays of out_cap entries, empty past n_out): slab, offsets, lens, src_index and out_chain ({"n_hdrs",
     "hdr_type", "hdr_off"}, slot-major over out_cap); batch() is the output as the batch dict the other calls take.
     hits: the per-status counters, if asked for."""
-
-    def __init__(self, **kw):
-        self.slab = self.offsets = self.lens = self.src_index = self.out_chain = self.hits = None
-        self.__dict__.update(kw)
-
-    def batch(self):
-        return dict(slab=self.slab, offsets=self.offsets, lens=self.lens)
 
 
 def _icmp_addr(a, size, what):
@@ -1973,10 +1990,13 @@ def _icmp_addr(a, size, what):
     return a
 
 
+_ICMPE = dict(what="icmp_errors", fn="pkt_icmp_err", result=IcmpErrResult, nc=schema.ICMPE_STATUS_COUNT,
+              no_write=schema.ICMPE_NO_WRITE, per_packet=(("status", np.uint8), ("out_index", np.uint32)), extra=None)
+
+
 def _icmp_errors(parser, batch, chain, reason, fwd_status, frag_status, mtu, src4, src6, ttl, tos, max4, max6, ident,
                  select, which_ip, plan_only, out_cap, dst_bytes, hits, host, stream):
     from . import _lib
-    L = _lib.load()
     if sum(x is not None for x in (reason, fwd_status, frag_status)) != 1:
         raise ValueError("icmp_errors: exactly one of reason, fwd_status and frag_status")
     code, cmap = reason, None
@@ -1984,95 +2004,14 @@ def _icmp_errors(parser, batch, chain, reason, fwd_status, frag_status, mtu, src
         code, cmap = fwd_status, schema.ICMP_MAP_FWD
     elif frag_status is not None:
         code, cmap = frag_status, schema.ICMP_MAP_FRAG
-    if hasattr(batch, "batch") and callable(batch.batch):
-        batch = batch.batch()
-    if isinstance(batch, (tuple, list)):
-        batch = dict(zip(("slab", "offsets", "lens"), batch))
-    g = lambda k: batch.get(k)  # noqa: E731
-    nc = schema.ICMPE_STATUS_COUNT
-    scalar = lambda v: isinstance(v, (int, np.integer))  # noqa: E731
-    if host:
-        b, keep = _host_batch(_lib, batch)
-        cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
-                np.ascontiguousarray(chain["hdr_off"], np.uint16))
-        ch = _lib.PktChain(*[c.ctypes.data for c in cols])
-        select = None if select is None else np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
-        empty = lambda k, dt: np.zeros(k, dt)  # noqa: E731
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
-        if not scalar(mtu):
-            mtu = np.ascontiguousarray(mtu, np.uint16)
-        if not scalar(code):
-            code = np.ascontiguousarray(code, np.uint8)
-    else:
-        torch = _torch()
-        b = parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
-        ch = parser._chain(chain)
-        dev = parser.torch_device
-        assert select is None or (select.is_cuda and select.dtype == torch.uint8 and select.is_contiguous()
-                                  and select.numel() >= b.n)
-        empty = lambda k, dt: torch.zeros(k, dtype=_tdtype(dt), device=dev)  # noqa: E731
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
-        ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
-        if not scalar(mtu):
-            assert mtu.is_cuda and mtu.dtype == torch.uint16 and mtu.is_contiguous() and mtu.numel() >= b.n
-        if not scalar(code):
-            assert code.is_cuda and code.dtype == torch.uint8 and code.is_contiguous() and code.numel() >= b.n
-    if hits is True:
-        hits = empty(nc, np.uint64)
-    if hits is not None and hits is not False:
-        assert ok(hits), f"icmp_errors: hits is a contiguous uint64 [{nc}] array"
-    else:
-        hits = None
     cfg = _lib.PktIcmpCfg()
     cfg.src4[:] = _icmp_addr(src4, 4, "src4")
     cfg.src6[:] = _icmp_addr(src6, 16, "src6")
     cfg.max4, cfg.max6, cfg.ident, cfg.ttl, cfg.tos = int(max4), int(max6), int(ident) & 0xFFFF, int(ttl), int(tos)
-    n = b.n
-    res = IcmpErrResult(status=empty(n, np.uint8), out_index=empty(n, np.uint32), hits=hits)
-    tot, cnt = ctypes.c_uint64(0), ctypes.c_uint64(0)
-
-    def call(fl, out, with_hits):
-        dst, cap = out.get("slab"), out.get("cap", 0)
-        oc = None
-        if out:
-            oc = _lib.PktChain(*[ptr(out["out_chain"][k]) for k in ("n_hdrs", "hdr_type", "hdr_off")])
-        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), fl, ctypes.byref(cfg),
-                None if scalar(code) else ptr(code), int(code) if scalar(code) else 0,
-                None if cmap is None else cmap.ctypes.data, None if scalar(mtu) else ptr(mtu),
-                int(mtu) if scalar(mtu) else 0, ptr(select), ptr(res.status), ptr(res.out_index),
-                dst.ctypes.data if host and dst is not None else dst.data_ptr() if dst is not None else None,
-                0 if dst is None else int(dst.size if host else dst.numel()), cap, ptr(out.get("offsets")), ptr(out.get("lens")),
-                ptr(out.get("src_index")), ctypes.byref(oc) if oc is not None else None,
-                ptr(hits) if with_hits else None, ctypes.byref(tot), ctypes.byref(cnt))
-        if host:
-            return L.pkt_icmp_err_host(*args)
-        return L.pkt_icmp_err_batch(parser._ctx, *args, parser._stream(stream))
-
-    def done(rc, what):
-        if rc == 0:
-            return
-        if host:
-            raise ValueError(f"pkt_icmp_err_host failed ({rc}); it needs {cnt.value} outputs and {tot.value} bytes")
-        parser._check(rc, what)
-
-    sized = out_cap is not None and dst_bytes is not None
-    if plan_only or not sized:
-        done(call(schema.ICMPE_NO_WRITE, {}, plan_only), "pkt_icmp_err_batch")
-        if plan_only:
-            res.n_out, res.bytes_out = cnt.value, tot.value
-            return res
-        out_cap = cnt.value if out_cap is None else out_cap
-        dst_bytes = tot.value if dst_bytes is None else dst_bytes
-    cap = max(1, int(out_cap))
-    out = dict(slab=empty(max(16, int(dst_bytes)), np.uint8), cap=cap, offsets=empty(cap, np.uint64),
-               lens=empty(cap, np.uint32), src_index=empty(cap, np.uint32),
-               out_chain=dict(n_hdrs=empty(cap, np.uint8), hdr_type=empty((schema.MAX_HDRS, cap), np.uint8),
-                              hdr_off=empty((schema.MAX_HDRS, cap), np.uint16)))
-    done(call(0, out, True), "pkt_icmp_err_batch")
-    out.pop("cap")
-    res.__dict__.update(out, n_out=cnt.value, bytes_out=tot.value)
-    return res
+    inputs = lambda per_packet: (ctypes.byref(cfg), *per_packet(code, np.uint8),  # noqa: E731
+                                 None if cmap is None else cmap.ctypes.data, *per_packet(mtu, np.uint16))
+    return _produce(parser, _ICMPE, batch, chain, select, which_ip, 0, inputs, plan_only, out_cap, dst_bytes, hits, host,
+                    stream)
 
 
 (REASM_WHOLE, REASM_JOINED, REASM_PENDING, REASM_SKIPPED, REASM_NO_IP, REASM_SPAN, REASM_BAD_HDR, REASM_TRUNC,
@@ -2080,7 +2019,7 @@ def _icmp_errors(parser, batch, chain, reason, fwd_status, frag_status, mtu, src
 REASM_NONE, REASM_ONLY_JOINED, REASM_NO_WRITE = schema.REASM_NONE, schema.REASM_ONLY_JOINED, schema.REASM_NO_WRITE
 
 
-class ReasmResult:
+class ReasmResult(_Produced):
     """What Parser.reassemble gives.  Per source packet: status (uint8: pktgpu.REASM_WHOLE / _JOINED / _PENDING /
     _SKIPPED / _NO_IP / _SPAN / _BAD_HDR / _TRUNC / _TOO_BIG) and out_index (uint32: the output carrying the packet's
     bytes; REASM_NONE where there is none).  The totals: n_out, bytes_out.  Unless plan_only, per output (arrays of
@@ -2088,94 +2027,21 @@ class ReasmResult:
     and out_chain ({"n_hdrs", "hdr_type", "hdr_off"}, slot-major over out_cap); batch() is the output as the batch
     dict the other calls take.  pending: the mask of the fragments to carry over to the next batch.  hits: the
     per-status counters, if asked for."""
-
-    def __init__(self, **kw):
-        self.slab = self.offsets = self.lens = self.src_index = self.nfrag = self.out_chain = self.hits = None
-        self.__dict__.update(kw)
-
-    def batch(self):
-        return dict(slab=self.slab, offsets=self.offsets, lens=self.lens)
+    nfrag = None
 
     @property
     def pending(self):
         return self.status == REASM_PENDING
 
 
+_REASM = dict(what="reassemble", fn="pkt_reasm", result=ReasmResult, nc=schema.REASM_STATUS_COUNT,
+              no_write=schema.REASM_NO_WRITE, per_packet=(("status", np.uint8), ("out_index", np.uint32)),
+              extra=("nfrag", np.uint32))
+
+
 def _reassemble(parser, batch, chain, select, which_ip, only_joined, plan_only, out_cap, dst_bytes, hits, host, stream):
-    from . import _lib
-    L = _lib.load()
-    if isinstance(batch, (tuple, list)):
-        batch = dict(zip(("slab", "offsets", "lens"), batch))
-    g = lambda k: batch.get(k)  # noqa: E731
-    nc = schema.REASM_STATUS_COUNT
-    if host:
-        b, keep = _host_batch(_lib, batch)
-        cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
-                np.ascontiguousarray(chain["hdr_off"], np.uint16))
-        ch = _lib.PktChain(*[c.ctypes.data for c in cols])
-        select = None if select is None else np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
-        empty = lambda k, dt: np.zeros(k, dt)  # noqa: E731
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
-    else:
-        torch = _torch()
-        b = parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
-        ch = parser._chain(chain)
-        dev = parser.torch_device
-        assert select is None or (select.is_cuda and select.dtype == torch.uint8 and select.is_contiguous()
-                                  and select.numel() >= b.n)
-        empty = lambda k, dt: torch.zeros(k, dtype=_tdtype(dt), device=dev)  # noqa: E731
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
-        ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
-    if hits is True:
-        hits = empty(nc, np.uint64)
-    if hits is not None and hits is not False:
-        assert ok(hits), f"reassemble: hits is a contiguous uint64 [{nc}] array"
-    else:
-        hits = None
-    n = b.n
-    res = ReasmResult(status=empty(n, np.uint8), out_index=empty(n, np.uint32), hits=hits)
-    flags = schema.REASM_ONLY_JOINED if only_joined else 0
-    tot, cnt = ctypes.c_uint64(0), ctypes.c_uint64(0)
-
-    def call(fl, out, with_hits):
-        dst, cap = out.get("slab"), out.get("cap", 0)
-        oc = None
-        if out:
-            oc = _lib.PktChain(*[ptr(out["out_chain"][k]) for k in ("n_hdrs", "hdr_type", "hdr_off")])
-        args = (ctypes.byref(b), ctypes.byref(ch), int(which_ip), fl, ptr(select), ptr(res.status), ptr(res.out_index),
-                dst.ctypes.data if host and dst is not None else dst.data_ptr() if dst is not None else None,
-                0 if dst is None else int(dst.size if host else dst.numel()), cap, ptr(out.get("offsets")), ptr(out.get("lens")),
-                ptr(out.get("src_index")), ptr(out.get("nfrag")), ctypes.byref(oc) if oc is not None else None,
-                ptr(hits) if with_hits else None, ctypes.byref(tot), ctypes.byref(cnt))
-        if host:
-            return L.pkt_reasm_host(*args)
-        return L.pkt_reasm_batch(parser._ctx, *args, parser._stream(stream))
-
-    def done(rc, what):
-        if rc == 0:
-            return
-        if host:
-            raise ValueError(f"pkt_reasm_host failed ({rc}); it needs {cnt.value} outputs and {tot.value} bytes")
-        parser._check(rc, what)
-
-    sized = out_cap is not None and dst_bytes is not None
-    if plan_only or not sized:
-        done(call(flags | schema.REASM_NO_WRITE, {}, plan_only), "pkt_reasm_batch")
-        if plan_only:
-            res.n_out, res.bytes_out = cnt.value, tot.value
-            return res
-        out_cap = cnt.value if out_cap is None else out_cap
-        dst_bytes = tot.value if dst_bytes is None else dst_bytes
-    cap = max(1, int(out_cap))
-    out = dict(slab=empty(max(16, int(dst_bytes)), np.uint8), cap=cap, offsets=empty(cap, np.uint64),
-               lens=empty(cap, np.uint32), src_index=empty(cap, np.uint32), nfrag=empty(cap, np.uint32),
-               out_chain=dict(n_hdrs=empty(cap, np.uint8), hdr_type=empty((schema.MAX_HDRS, cap), np.uint8),
-                              hdr_off=empty((schema.MAX_HDRS, cap), np.uint16)))
-    done(call(flags, out, True), "pkt_reasm_batch")
-    out.pop("cap")
-    res.__dict__.update(out, n_out=cnt.value, bytes_out=tot.value)
-    return res
+    return _produce(parser, _REASM, batch, chain, select, which_ip, schema.REASM_ONLY_JOINED if only_joined else 0,
+                    lambda per_packet: (), plan_only, out_cap, dst_bytes, hits, host, stream)
 
 
 # ----------------------------------------------------------------- PacketSlice-style host views

@@ -235,6 +235,25 @@ def layout(items, kind="indexed", seed=3, stride=None):
     return C.batch(slab, lens=[len(p) for p, _ in items], stride=stride, n=n), chain
 
 
+def tiled(items, n, stride=64):
+    """(batch, chain) of n fixed-stride packets with lens: the few `items`, which share one header list, repeated in
+    turn.  Built with numpy alone: layout()'s per-packet loops are too slow at the sizes where the tile scan and the
+    counting grid take their other paths."""
+    hdrs = items[0][1]
+    assert all(h == hdrs for _, h in items) and all(len(p) <= stride for p, _ in items)
+    rows = np.full((len(items), stride), 0xEE, np.uint8)
+    for j, (p, _) in enumerate(items):
+        rows[j, :len(p)] = np.frombuffer(p, np.uint8)
+    reps = -(-n // len(items))
+    slab = np.tile(rows, (reps, 1))[:n].reshape(-1)
+    lens = np.tile(np.array([len(p) for p, _ in items], np.uint32), reps)[:n]
+    chain = dict(n_hdrs=np.full(n, len(hdrs), np.uint8), hdr_type=np.zeros((MAXH, n), np.uint8),
+                 hdr_off=np.zeros((MAXH, n), np.uint16))
+    for j, (t, o) in enumerate(hdrs):
+        chain["hdr_type"][j], chain["hdr_off"][j] = t, o
+    return C.batch(slab, lens=lens, stride=stride, n=n), chain
+
+
 MTUS = (28, 68, 576, 1500)
 
 

@@ -154,6 +154,27 @@ def test_mix_against_the_model_and_the_host_twin(P, kind):
     assert int(got["hits"].sum()) == b["n"]
 
 
+def test_4098_tiles_the_scan_in_two_rounds_and_the_counting_grid_capped(P):
+    """4096 * 256 + 256 + 3 packets: the one-block scan of the tile sums takes 4096 tiles a round, so its second round
+    holds two tiles, the last one ragged, and first[] / out_off check every tile's prefix across the two rounds; with
+    hits the decision launch is capped at 1280 blocks, so a block takes up to four tiles.  60-byte Ether / IPv4 / UDP
+    packets at stride 64, mtu 0 (FITS) and 28 (SPLIT into 4) in turn, every 61st packet selected (about four a tile, at
+    varying places).  Against the host twin alone: the Python model is too slow at this size, and test_frag_host.py
+    holds the twin to it."""
+    n = 4096 * 256 + 256 + 3
+    b, ch = G.tiled([G.v4(26, seed=k) for k in range(4)], n)
+    mtu = np.where(np.arange(n) % 2 == 0, 0, 28).astype(np.uint16)
+    sel = (np.arange(n) % 61 == 0).astype(np.uint8)
+    rc, got, intact = run(P, b, ch, mtu, sel)
+    assert rc == 0 and intact
+    h = twin(b, ch, mtu, sel)
+    counts = np.bincount(h["status"], minlength=G.NSTATUS)
+    assert counts[G.FITS] > 8000 and counts[G.SPLIT] > 8000 and counts[G.SKIPPED] == n - counts[G.FITS] - counts[G.SPLIT]
+    assert set(h["nfrag"][h["status"] == G.SPLIT]) == {4} and h["n_out"] == counts[G.FITS] + 4 * counts[G.SPLIT]
+    same_as_twin(got, h, "4098 tiles")
+    assert np.array_equal(got["hits"], counts) and (got["dst"][h["bytes_out"]:] == FILL).all()
+
+
 def test_two_runs_give_identical_bytes_and_arrays(P):
     b, ch, mtu, sel, want = mix("stride")
     r1, g1, i1 = run(P, b, ch, mtu, sel)

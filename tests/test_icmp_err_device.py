@@ -162,6 +162,21 @@ def test_mix_against_the_model_and_the_host_twin(P, kind, which, nosrc):
     assert int(got["hits"].sum()) == b["n"]
 
 
+def test_1282_tiles_a_counting_block_takes_two(P):
+    """1280 * 256 + 257 packets: with hits the decision launch is capped at 1280 blocks, so two of them take a second
+    tile, the last one ragged.  52-byte Ether / IPv4 / UDP packets at stride 64, one reason for all of them, every 61st
+    selected.  Against the host twin alone: the Python model is too slow at this size, and test_icmp_err_host.py holds
+    the twin to it."""
+    n = 1280 * 256 + 257
+    b, ch = I.G.tiled([I.pkt(I.udp(18, seed=k)) for k in range(4)], n)
+    sel = (np.arange(n) % 61 == 0).astype(np.uint8)
+    rc, got, intact = run(P, b, ch, I.R_TIME_EXCEEDED, CF, 0, None, sel)
+    assert rc == 0 and intact
+    same_as_twin(got, b, ch, I.R_TIME_EXCEEDED, CF, 0, None, sel, 0, "1282 tiles")
+    assert got["n_out"] == -(-n // 61) and got["hits"][I.SENT] == got["n_out"] and got["hits"][I.SKIPPED] == n - got["n_out"]
+    assert (got["dst"][got["bytes_out"]:] == FILL).all()
+
+
 def test_two_runs_give_identical_bytes_and_arrays(P):
     b, ch, code, mtu, sel, cf, want = mix("stride", I.LAST)
     r1, g1, i1 = run(P, b, ch, code, cf, mtu, I.MAP, sel, I.LAST)

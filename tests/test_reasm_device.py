@@ -166,6 +166,22 @@ def test_mix_against_the_model_and_the_host_twin(P, kind):
     assert int(got["hits"].sum()) == b["n"]
 
 
+def test_1282_tiles_a_counting_block_takes_two(P):
+    """1280 * 256 + 257 packets: with hits the counting launch is capped at 1280 blocks, so two of them take a second
+    tile, the last one ragged.  Whole 60-byte packets (no fragments) at stride 64, every 61st selected.  Against the
+    host twin alone: the Python model is too slow at this size, and test_reasm_host.py holds the twin to it."""
+    n = 1280 * 256 + 257
+    b, ch = G.tiled([G.v4(26, seed=k) for k in range(4)], n)
+    sel = (np.arange(n) % 61 == 0).astype(np.uint8)
+    rc, got, intact = run(P, b, ch, sel)
+    assert rc == 0 and intact
+    h = twin(b, ch, sel)
+    counts = np.bincount(h["status"], minlength=R.NSTATUS)
+    assert counts[R.WHOLE] == h["n_out"] == -(-n // 61) and counts[R.SKIPPED] == n - counts[R.WHOLE]
+    same_as_twin(got, h, "1282 tiles")
+    assert np.array_equal(got["hits"], counts) and (got["dst"][h["bytes_out"]:] == FILL).all()
+
+
 def test_two_runs_give_identical_bytes_and_arrays(P):
     b, ch, sel, want = mix("indexed")
     r1, g1, i1 = run(P, b, ch, sel)
