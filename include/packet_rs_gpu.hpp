@@ -381,6 +381,28 @@ class Parser {
               ctx_, "pkt_fwd_batch");
     }
 
+    // A NAPT44 session table on this context's device (pkt_nat_create): `pool` holds 4 wire bytes per outside address.
+    // The caller destroys it with pkt_nat_destroy after the calls queued on it; pkt_nat_expire / _count / _export /
+    // _clear take the handle as it is.
+    pkt_nat_t* nat(const std::vector<uint8_t>& pool, uint32_t port_lo, uint32_t port_hi, uint64_t slots,
+                   const std::vector<pkt_nat_static_t>& statics = {}) {
+        pkt_nat_t* t = nullptr;
+        check(pkt_nat_create(ctx_, pool.data(), (uint32_t)(pool.size() / 4), port_lo, port_hi, slots,
+                             statics.empty() ? nullptr : statics.data(), (uint32_t)statics.size(), &t), ctx_, "pkt_nat_create");
+        return t;
+    }
+
+    // The translation of a parsed batch, in place (pkt_nat_batch): packet i goes inside -> outside (PKT_NAT_OUT) or
+    // back (PKT_NAT_IN) as dir[i] says, or as dir_all says when `dir` is NULL; `now` is the caller's clock in seconds.
+    // status / entry / created / hits / bytes may each be NULL.  Asynchronous on `s`; one call at a time per handle.
+    void translate(pkt_nat_t* t, const pkt_batch_t& b, const pkt_chain_t& chain, const uint8_t* dir, uint32_t dir_all,
+                   uint32_t now, uint8_t* status = nullptr, uint32_t* entry = nullptr, uint8_t* created = nullptr,
+                   const uint8_t* select = nullptr, uint32_t which_ip = 0, uint32_t flags = 0, uint64_t* hits = nullptr,
+                   uint64_t* bytes = nullptr, hipStream_t s = nullptr) {
+        check(pkt_nat_batch(t, &b, &chain, which_ip, flags, dir_all, dir, select, now, status, entry, created, hits, bytes, s),
+              ctx_, "pkt_nat_batch");
+    }
+
     // What Parser::fragment reports: the outputs and their rounded bytes (the capacities to retry with when `fits`
     // is false: the outputs did not fit out_cap / dst_len, and dst and the per-output arrays are unspecified).
     struct FragTotals {

@@ -720,7 +720,9 @@ int pkt_edit_host(const pkt_batch_t *batch, const pkt_out_t *parsed, const pkt_e
  *    NULL chain column), n >= 2^32, unknown flag bits, KEEP_ZERO_UDP without UPDATE, a bad `which`.  n == 0
  *    succeeds and launches nothing.
  * Asynchronous on `stream`, like pkt_edit_batch: no host wait, no summary and no ctx state.
- * pkt_l4_checksum_host is the same operation on HOST pointers and needs no device or ctx. */
+ * pkt_l4_checksum_host is the same operation on HOST pointers and needs no device or ctx.
+ * Out of scope: incremental (RFC 1624) updates after a field rewrite: pkt_fwd_batch (the ttl) and pkt_nat_batch (an
+ * address and a port, with the TCP / UDP / ICMP checksum; no payload byte is read) are the calls that make them. */
 typedef enum pkt_l4_status {
     PKT_L4_OK        = 0, /* stored == calc (or stored 0xFFFF with calc 0: the two encodings of zero) */
     PKT_L4_BAD       = 1,
@@ -1180,7 +1182,8 @@ const char *pkt_lpm_last_error(const pkt_lpm_t *lpm);
  * pkt_fwd_host is the same operation on HOST pointers: no ctx, no device, no handle.  Its lpm, if given, must be a
  * handle from pkt_lpm_create_host; the slab's 16-byte alignment rule is waived, as for that handle.
  * Out of scope: VLAN push or rewrite (pkt_edit_batch / pkt_set_fields); ICMP time-exceeded and fragmentation-needed
- * generation (pkt_icmp_err_batch, below, takes this call's status array; fragmentation itself is pkt_frag_batch, below: it takes the PKT_FWD_MTU packets); ECMP; per-adjacency counters (a bincount of adj_index); NAT; IPv4 options and
+ * generation (pkt_icmp_err_batch, below, takes this call's status array; fragmentation itself is pkt_frag_batch, below: it takes the PKT_FWD_MTU packets); ECMP; per-adjacency counters (a bincount of adj_index); NAT (pkt_nat_batch, below,
+ * before this call); IPv4 options and
  * IPv6 extension headers (the walk models neither). */
 typedef struct pkt_fwd_adj {       /* 20 bytes */
     uint8_t  dmac[6];              /* written to the Ether header's bytes 0..5 */
@@ -1674,6 +1677,157 @@ int pkt_icmp_err_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32
                       uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
                       const pkt_chain_t *out_chain,
                       uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
+
+/* ---- pkt_nat_*: NAPT44 sessions and translation over a parsed batch ----
+ * The step of an edge router between "parsed" and "routed": keep the sessions, allocate the outside ports, rewrite
+ * addresses and ports in place and update the IPv4 and TCP / UDP / ICMP checksums incrementally.  The reference defines
+ * nothing here, so this header fixes the semantics.
+ *
+ * Scope: NAT44 with port translation for TCP, UDP and ICMP echo (the echo identifier plays the port).  Mapping and
+ * filtering are endpoint-independent (RFC 4787 REQ-1): a session is (proto, inside addr, inside port) <-> (proto,
+ * outside addr, outside port), whatever the remote end.  Protocol indexes: p = 0 TCP (6), 1 UDP (17), 2 ICMP (1).
+ *
+ * pkt_nat_create: blocking, and the only allocating call.  pool: naddr (1..64) outside IPv4 addresses, 4 wire bytes
+ * each, distinct.  The dynamic ports are port_lo..port_hi (1 <= lo <= hi <= 65535) for each of the three protocols,
+ * nports = hi - lo + 1.  A pool entry is e in [0, E), E = naddr * nports: its address is pool[e / nports], its port
+ * port_lo + e % nports.  slots: the forward table's size, a power of two in 64..2^26.  statics: nstatic (<= 4096)
+ * permanent mappings (port forwards; ports in host byte order; the outside address may be any address).
+ * PKT_ERR_INVALID_ARG with a text starting "pkt_nat" (pkt_ctx_last_error for pkt_nat_create, pkt_nat_last_error(NULL)
+ * on the calling thread for pkt_nat_create_host): sizes out of range, NULL pool, NULL statics with nstatic > 0, duplicate
+ * pool addresses, a static whose proto is not 6 / 17 / 1, a non-zero `zero`, a duplicate inside endpoint per proto, a
+ * duplicate outside endpoint per proto, an outside endpoint that is a dynamic pool entry (a pool address with its port
+ * in [lo, hi]), nstatic > slots / 2.  pkt_nat_create_host gives the same handle on host memory: every later call then
+ * takes HOST pointers, runs sequentially and touches no device (the pkt_flow_table_create_host pattern; the slab's
+ * alignment rule is waived).
+ *
+ * pkt_nat_batch: asynchronous on `stream`, one call at a time per handle, no host readback, no allocation.  dir: device
+ * uint8_t[n] or NULL (every packet takes dir_all); PKT_NAT_OUT = 0 (inside to outside), PKT_NAT_IN = 1, any other value
+ * skips the packet: a pkt_match_batch action maps onto it directly.  now: the caller's clock, seconds.
+ * Per packet i the first test that applies gives status[i]; a packet whose status is not PKT_NAT_OK is not written.
+ *  1. select != NULL && select[i] == 0, or its dir >= 2: PKT_NAT_SKIPPED.
+ *  2. The IP entry is found exactly as in pkt_flow_key_batch (which_ip, PKT_FLOW_LAST included, over min(n_hdrs,
+ *     PKT_MAX_HDRS) entries; a which_ip in 16..0xFE is refused).  None: PKT_NAT_NO_IP.  It is IPv6: PKT_NAT_IPV6.  Its 20
+ *     bytes are not inside the packet (under the pkt_batch_t clamp rules): PKT_NAT_SPAN.
+ *  3. Byte 0 != 0x45: PKT_NAT_BAD_HDR (pkt_frag_batch's rule: no options).
+ *  4. (bytes 6..7 & 0x3FFF) != 0: PKT_NAT_FRAGMENT, the first fragment included (pkt_reasm_batch first).
+ *  5. Byte 9 is 6 / 17 / 1 and the list entry right after the IP entry is PKT_HDR_TCP / _UDP / _ICMP respectively,
+ *     otherwise PKT_NAT_NO_L4.  The L4 bytes needed are 20 (TCP), 8 (UDP), 8 (ICMP) from that entry's hdr_off; not
+ *     inside the packet: PKT_NAT_SPAN.  ICMP whose type byte is neither 8 nor 0: PKT_NAT_NO_L4.  The "port" is bytes
+ *     0..1 (source) / 2..3 (destination) of TCP and UDP, bytes 4..5 of ICMP in both directions.
+ *  6. OUT: the key is (p, source address, source port).  A session or static with that inside endpoint exists:
+ *     PKT_NAT_OK.  Otherwise a session is created: no room in the forward table: PKT_NAT_TABLE_FULL; no free pool entry
+ *     of protocol p: PKT_NAT_EXHAUSTED; else PKT_NAT_OK.
+ *  7. IN: the destination endpoint equals a static's outside endpoint: PKT_NAT_OK.  It is a dynamic pool entry that is
+ *     mapped: PKT_NAT_OK; one that is free: PKT_NAT_NO_SESSION.  Anything else: PKT_NAT_NOT_OURS (the packet is for
+ *     the router itself or for someone else; it is untouched).
+ * Allocation is exact and the same from run to run.  The model is sequential: take the OUT packets of the call in index
+ * order; a packet whose key has no session takes the first free entry of protocol p at or after cursor[p], circularly,
+ * marks it, sets cursor[p] = (e + 1) mod E and last_seen = now.  With no free entry the packet is EXHAUSTED and no
+ * session exists (a later packet of the key tries again and, within the call, fails again).  After all OUT packets the
+ * IN packets are looked up: an IN packet sees the sessions this call's OUT packets created, whatever the two indices.
+ * Every OK packet of either direction sets its session's last_seen = max(last_seen, now); statics have no clock.
+ * The forward table holds the statics' inside endpoints, the sessions, and the keys that were EXHAUSTED since the last
+ * pkt_nat_expire / pkt_nat_clear (those two drop them).  Once any packet of a call is TABLE_FULL, which keys lost is
+ * unspecified (pkt_flow_table's rule), and so is which entries that call's new sessions got; every other rule holds and
+ * the sessions of earlier calls stay exact.
+ * The writes of an OK packet (none with PKT_NAT_NO_WRITE, which still creates and refreshes):
+ *  - OUT: the source address (IP bytes 12..15) and the source port / id; IN: the destination address (bytes 16..19)
+ *    and the destination port / id.
+ *  - The IPv4 checksum (bytes 10..11) and the L4 checksum (TCP bytes 16..17, UDP 6..7, ICMP 2..3), by RFC 1624 eq. 3
+ *    over the rewritten 16-bit words m_k -> m'_k: the two address words for the IPv4 checksum; the two address words
+ *    (pseudo-header) and the port word for TCP and UDP; the id word alone for ICMP.  s = (~HC & 0xFFFF) +
+ *    sum(~m_k & 0xFFFF) + sum(m'_k), folded twice (s = (s & 0xFFFF) + (s >> 16)), HC' = ~s & 0xFFFF.  The words are
+ *    always these, whether or not a value differs.  As in pkt_fwd_batch a checksum that was wrong stays wrong by the
+ *    same amount and no payload byte is read: a capture cut by snaplen translates correctly.
+ *  - UDP: a stored checksum of 0 means none and stays 0; a computed HC' of 0 is stored as 0xFFFF (RFC 768).
+ *  - Lengths do not change, so the chain columns stay valid: pkt_fwd_batch, pkt_l4_checksum_batch, pkt_flow_key_batch,
+ *    pkt_dispatch_batch and pkt_pcap_write follow with no second parse.
+ *  - Stores are narrow: only the bytes named above, in the packet's own IP header and L4 header, at any alignment.
+ *    Packets of one batch must not overlap.  Columns that are not a parse of the batch give unspecified packet bytes,
+ *    never an access outside the packet.
+ * Outputs: device arrays of n elements, each may be NULL.  status: uint8_t.  entry: uint32_t, p * E + e for a dynamic
+ * session, PKT_NAT_STATIC | index for a static, PKT_NAT_NONE for a packet that is not OK.  created: uint8_t, 1 iff the
+ * packet is the lowest-index packet of a session this call created.  hits / bytes: uint64_t[PKT_NAT_STATUS_COUNT],
+ * 8-byte aligned, ADDED to exactly as pkt_fwd_batch's are: every call adds exactly n to sum(hits).
+ * PKT_ERR_INVALID_ARG before any launch (the text, starting "pkt_nat", in pkt_nat_last_error and, for a device handle,
+ * in pkt_ctx_last_error of its ctx): pkt_fwd_batch's batch and slab rules, a NULL chain or, with n > 0, chain column,
+ * n >= 2^32, a bad which_ip, unknown flag bits, dir_all >= 2 with dir == NULL, hits / bytes not 8-byte aligned.  n == 0
+ * succeeds and launches nothing.
+ *
+ * pkt_nat_expire (blocking): a dynamic session of protocol p with idle[p] != 0 and last_seen + idle[p] <= now (64-bit
+ * arithmetic) is removed and its pool entry freed; *n_expired (may be NULL) = how many.  Cursors stay where they are;
+ * statics never expire.  The forward table is rebuilt from the survivors into a second buffer the handle owns, so its
+ * probe chains stay sound and no tombstone is ever reused.  pkt_nat_count (blocking): the dynamic sessions per
+ * protocol.  pkt_nat_export (blocking): min(cap, total) records written, *n_out = total: the dynamic sessions in
+ * ascending (p, e), then the statics in array order (flags = PKT_NAT_REC_STATIC, last_seen = 0); the order is exact.
+ * `records` is device memory for a device handle.  pkt_nat_clear (asynchronous): no dynamic session, cursors 0.
+ * pkt_nat_destroy is the caller's to order after the queued calls.  idle, n_expired, counts and n_out are HOST memory.
+ * On the device a lane owns a packet and no lane waits for another; kernel boundaries publish: (1) classify, find or
+ * claim the key's forward slot by a 64-bit compare-and-swap and put the lowest index into the slot, (2) count the
+ * creators per tile and protocol, (3) count the free pool entries per 1024-entry block in circular order from the
+ * cursor, (4) one block scans both, (5) the j-th creator of a protocol takes the j-th free entry, (6) translate.
+ * (3) to (5) exit at once when the call creates nothing; that is decided on the device.
+ * Out of scope: NAT64 / NAT66; hairpinning; paired address pooling with more than one pool address (RFC 4787 REQ-2);
+ * port preservation and parity; TCP state tracking and per-state timeouts; the packets quoted in ICMP errors (RFC
+ * 5508); ALGs; per-session counters (a pkt_flow_table beside it); IPv4 options. */
+typedef struct pkt_nat pkt_nat_t;
+typedef struct pkt_nat_static {    /* 16 bytes */
+    uint8_t  in_addr[4];           /* wire bytes */
+    uint8_t  out_addr[4];
+    uint16_t in_port;              /* host byte order; the echo identifier for ICMP */
+    uint16_t out_port;
+    uint8_t  proto;                /* 6, 17 or 1 */
+    uint8_t  zero[3];
+} pkt_nat_static_t;
+typedef struct pkt_nat_record {    /* 20 bytes */
+    uint8_t  in_addr[4];
+    uint8_t  out_addr[4];
+    uint16_t in_port;
+    uint16_t out_port;
+    uint8_t  proto;
+    uint8_t  flags;                /* PKT_NAT_REC_STATIC */
+    uint16_t zero;
+    uint32_t last_seen;
+} pkt_nat_record_t;
+typedef enum pkt_nat_status {
+    PKT_NAT_OK         = 0,
+    PKT_NAT_SKIPPED    = 1,  /* select[i] == 0, or a dir that is neither OUT nor IN */
+    PKT_NAT_NO_IP      = 2,  /* the chain has no such IP entry */
+    PKT_NAT_SPAN       = 3,  /* the IP header or the L4 bytes do not lie inside the packet */
+    PKT_NAT_IPV6       = 4,
+    PKT_NAT_BAD_HDR    = 5,  /* IPv4 byte 0 != 0x45 */
+    PKT_NAT_FRAGMENT   = 6,  /* any fragment */
+    PKT_NAT_NO_L4      = 7,  /* not TCP / UDP / ICMP echo, or the chain's next entry is not that header */
+    PKT_NAT_NO_SESSION = 8,  /* IN: a dynamic pool entry that is free */
+    PKT_NAT_NOT_OURS   = 9,  /* IN: neither a static's outside endpoint nor a dynamic pool entry */
+    PKT_NAT_EXHAUSTED  = 10, /* OUT: no free pool entry of the protocol */
+    PKT_NAT_TABLE_FULL = 11  /* OUT: no room in the forward table */
+} pkt_nat_status_t;
+#define PKT_NAT_STATUS_COUNT 12
+#define PKT_NAT_OUT        0u
+#define PKT_NAT_IN         1u
+#define PKT_NAT_NO_WRITE   1u            /* flags: create, refresh and decide, store nothing into the slab */
+#define PKT_NAT_NONE       0xFFFFFFFFu   /* entry[i] of a packet that is not OK */
+#define PKT_NAT_STATIC     0x80000000u   /* entry[i] = PKT_NAT_STATIC | the static's index */
+#define PKT_NAT_REC_STATIC 1u
+#define PKT_NAT_MAX_ADDR   64u
+#define PKT_NAT_MAX_STATIC 4096u
+size_t pkt_sizeof_nat_static(void);
+size_t pkt_sizeof_nat_record(void);
+int pkt_nat_create(pkt_ctx_t *ctx, const uint8_t *pool, uint32_t naddr, uint32_t port_lo, uint32_t port_hi,
+                   uint64_t slots, const pkt_nat_static_t *statics, uint32_t nstatic, pkt_nat_t **nat);
+int pkt_nat_create_host(const uint8_t *pool, uint32_t naddr, uint32_t port_lo, uint32_t port_hi, uint64_t slots,
+                        const pkt_nat_static_t *statics, uint32_t nstatic, pkt_nat_t **nat);
+int pkt_nat_batch(pkt_nat_t *nat, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                  uint32_t flags, uint32_t dir_all, const uint8_t *dir, const uint8_t *select, uint32_t now,
+                  uint8_t *status, uint32_t *entry, uint8_t *created, uint64_t *hits, uint64_t *bytes,
+                  void *stream);
+int pkt_nat_expire(pkt_nat_t *nat, uint32_t now, const uint32_t idle[3], uint64_t *n_expired);
+int pkt_nat_count(pkt_nat_t *nat, uint64_t counts[3]);
+int pkt_nat_export(pkt_nat_t *nat, pkt_nat_record_t *records, uint64_t cap, uint64_t *n_out);
+int pkt_nat_clear(pkt_nat_t *nat, void *stream);
+int pkt_nat_destroy(pkt_nat_t *nat);
+const char *pkt_nat_last_error(const pkt_nat_t *nat);
 
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);

@@ -17,6 +17,7 @@
 #include "pktgpu_reasm.hpp"
 #include "pktgpu_scan.hpp"
 #include "pktgpu_icmp.hpp"
+#include "pktgpu_nat.hpp"
 
 namespace {
 
@@ -1093,6 +1094,250 @@ int pkt_fwd_host(const pkt_fwd_adj_t* adj, uint32_t nadj, const pkt_batch_t* b, 
     }
     return PKT_SUCCESS;
 }
+
+// ---- pkt_nat_*: the public calls, and the host handle, which is the sequential model of include/pktgpu.h itself (the
+// device handle: pktgpu_nat.hip).  The decision, the arithmetic and the stores are pktgpu_nat.hpp's, which the kernels
+// share.
+size_t pkt_sizeof_nat_static(void) { return sizeof(pkt_nat_static_t); }
+size_t pkt_sizeof_nat_record(void) { return sizeof(pkt_nat_record_t); }
+
+static thread_local std::string t_nat_create_err;  // pkt_nat_last_error(NULL): the thread's last failed create_host
+
+namespace {
+
+// the slot of `key` in a host forward table, claimed when `claim` and there is room; kNatNoSlot: none
+uint32_t nat_host_slot(NatView& v, uint64_t key, bool claim) {
+    uint64_t pos = nat_home(key, v.slots);
+    for (uint64_t probes = 0; probes < v.slots; probes++, pos = (pos + 1) & (v.slots - 1)) {
+        if (v.fkey[pos] == key) return (uint32_t)pos;
+        if (v.fkey[pos] == 0) {
+            if (!claim) return kNatNoSlot;
+            v.fkey[pos] = key;
+            return (uint32_t)pos;
+        }
+    }
+    return kNatNoSlot;
+}
+
+// the empty forward table with the statics and the mapped entries in it
+void nat_host_rebuild(pkt_nat* t) {
+    NatView& v = t->v;
+    std::fill(t->h_fkey.begin(), t->h_fkey.end(), 0ull);
+    std::fill(t->h_fval.begin(), t->h_fval.end(), PKT_NAT_NONE);
+    for (uint32_t k = 0; k < v.nstatic; k++) v.fval[nat_host_slot(v, v.st_in[k], true)] = PKT_NAT_STATIC | k;
+    for (uint32_t ent = 0; ent < 3 * v.E; ent++)
+        if (v.rev[ent]) v.fval[nat_host_slot(v, v.rev[ent], true)] = ent;
+}
+
+void nat_host_clear(pkt_nat* t) {
+    std::fill(t->h_rev.begin(), t->h_rev.end(), 0ull);
+    std::fill(t->h_seen.begin(), t->h_seen.end(), 0u);
+    std::fill(t->h_used.begin(), t->h_used.end(), 0u);
+    std::fill(t->h_cursor.begin(), t->h_cursor.end(), 0u);
+    nat_host_rebuild(t);
+}
+
+int nat_host_batch(pkt_nat* t, const NatCall& c) {
+    NatView& v = t->v;
+    const uint64_t n = c.n;
+    uint8_t* slab = const_cast<uint8_t*>(c.src.slab);
+    std::vector<uint8_t> st1(n, PKT_NAT_OK), made(n, 0);
+    std::vector<uint32_t> ent1(n, PKT_NAT_NONE);
+    bool none_free[3] = {false, false, false};  // nothing is freed within a call
+    for (uint64_t i = 0; i < n; i++) {  // the OUT packets in index order
+        if (nat_dir(c, i) != PKT_NAT_OUT) continue;
+        const uint64_t off = pkt_off(c.src, i);
+        const NatPkt k = nat_classify(slab + off, pkt_len(c.src, i, off), c.n_hdrs, c.hdr_type, c.hdr_off, n, i, c.which, 0);
+        if (k.st != PKT_NAT_OK) continue;
+        const uint32_t slot = nat_host_slot(v, k.key, true);
+        if (slot == kNatNoSlot) {
+            st1[i] = PKT_NAT_TABLE_FULL;
+            continue;
+        }
+        if (v.fval[slot] == PKT_NAT_NONE) {  // no session: the first free entry at or after the cursor, circularly
+            uint32_t e = v.E;
+            uint32_t* used = v.used + k.p * v.W;
+            for (uint32_t s = 0; s < v.E && !none_free[k.p]; s++) {
+                const uint32_t x = (v.cursor[k.p] + s) % v.E;
+                if (!(used[x >> 5] >> (x & 31u) & 1u)) {
+                    e = x;
+                    break;
+                }
+            }
+            if (e == v.E) {
+                none_free[k.p] = true;
+                st1[i] = PKT_NAT_EXHAUSTED;
+                continue;
+            }
+            used[e >> 5] |= 1u << (e & 31u);
+            v.cursor[k.p] = (e + 1) % v.E;
+            v.fval[slot] = k.p * v.E + e;
+            v.rev[k.p * v.E + e] = k.key;
+            v.seen[k.p * v.E + e] = c.now;
+            made[i] = 1;
+        }
+        ent1[i] = v.fval[slot];
+    }
+    const bool write = !(c.flags & PKT_NAT_NO_WRITE);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t off = pkt_off(c.src, i);
+        const uint32_t len = pkt_len(c.src, i, off);
+        const uint32_t d = nat_dir(c, i);
+        uint32_t st = PKT_NAT_SKIPPED, ent = PKT_NAT_NONE;
+        if (d < 2) {
+            const NatPkt k = nat_classify(slab + off, len, c.n_hdrs, c.hdr_type, c.hdr_off, n, i, c.which, d);
+            st = k.st;
+            if (st == PKT_NAT_OK) {
+                if (d == PKT_NAT_OUT) {
+                    st = st1[i];
+                    ent = ent1[i];
+                } else {
+                    ent = nat_in_find(v, k.key, st);
+                }
+            }
+            if (st == PKT_NAT_OK) {
+                if (!(ent & PKT_NAT_STATIC) && v.seen[ent] < c.now) v.seen[ent] = c.now;
+                if (write) nat_rewrite(slab + off + k.ipo, slab + off + k.l4o, k.p, d, nat_target(v, ent, k.p, d));
+            }
+        }
+        if (c.status) c.status[i] = (uint8_t)st;
+        if (c.entry) c.entry[i] = ent;
+        if (c.created) c.created[i] = made[i];
+        if (c.hits) c.hits[st] += 1;
+        if (c.bytes) c.bytes[st] += len;
+    }
+    return PKT_SUCCESS;
+}
+
+}  // namespace
+
+int pkt_nat_create_host(const uint8_t* pool, uint32_t naddr, uint32_t port_lo, uint32_t port_hi, uint64_t slots,
+                        const pkt_nat_static_t* statics, uint32_t nstatic, pkt_nat_t** out) {
+    if (!out) {
+        t_nat_create_err = "pkt_nat_create_host: null argument";
+        return PKT_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    pkt_nat* t = new pkt_nat;
+    if (const char* msg = nat_create_error(pool, naddr, port_lo, port_hi, slots, statics, nstatic, t->img)) {
+        t_nat_create_err = std::string("pkt_nat_create_host: ") + msg;
+        delete t;
+        return PKT_ERR_INVALID_ARG;
+    }
+    const NatImage& g = t->img;
+    t->h_fkey.resize(slots);
+    t->h_fval.resize(slots);
+    t->h_ffirst.resize(slots, ~0u);
+    t->h_rev.resize(3ull * g.E);
+    t->h_seen.resize(3ull * g.E);
+    t->h_used.resize(3ull * g.W);
+    t->h_cursor.resize(3);
+    NatView& v = t->v;
+    nat_view_config(v, g);
+    v.fkey = t->h_fkey.data(), v.fval = t->h_fval.data(), v.ffirst = t->h_ffirst.data();
+    v.rev = t->h_rev.data(), v.seen = t->h_seen.data(), v.used = t->h_used.data(), v.cursor = t->h_cursor.data();
+    v.pool = g.pool.data(), v.pool_sorted = g.pool_sorted.data();
+    v.st_in = g.st_in.data(), v.st_out = g.st_out.data(), v.sin_key = g.sin_key.data(), v.sin_idx = g.sin_idx.data();
+    nat_host_clear(t);
+    *out = t;
+    return PKT_SUCCESS;
+}
+
+int pkt_nat_batch(pkt_nat_t* t, const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
+                  uint32_t dir_all, const uint8_t* dir, const uint8_t* select, uint32_t now, uint8_t* status,
+                  uint32_t* entry, uint8_t* created, uint64_t* hits, uint64_t* bytes, void* stream) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (const char* msg = nat_call_error(b, chain, which_ip, flags, dir_all, dir, hits, bytes))
+        return nat_fail(t, "pkt_nat_batch", msg);
+    if (b->n == 0) return PKT_SUCCESS;
+    if (const char* msg = nat_batch_error(b, chain, t->ops != nullptr)) return nat_fail(t, "pkt_nat_batch", msg);
+    const NatCall c{batch_src(b), b->n, chain->n_hdrs, chain->hdr_type, chain->hdr_off, which_ip, flags, dir_all, now,
+                    dir, select, status, entry, created, hits, bytes};
+    return t->ops ? t->ops->batch(t, c, stream) : nat_host_batch(t, c);
+}
+
+int pkt_nat_expire(pkt_nat_t* t, uint32_t now, const uint32_t idle[3], uint64_t* n_expired) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (!idle) return nat_fail(t, "pkt_nat_expire", "null idle");
+    if (t->ops) return t->ops->expire(t, now, idle, n_expired);
+    NatView& v = t->v;
+    uint64_t gone = 0;
+    for (uint32_t p = 0; p < 3; p++)
+        for (uint32_t e = 0; e < v.E && idle[p]; e++) {
+            const uint32_t ent = p * v.E + e;
+            if (!v.rev[ent] || (uint64_t)v.seen[ent] + idle[p] > now) continue;
+            v.rev[ent] = 0;
+            v.used[p * v.W + (e >> 5)] &= ~(1u << (e & 31u));
+            gone++;
+        }
+    nat_host_rebuild(t);
+    if (n_expired) *n_expired = gone;
+    return PKT_SUCCESS;
+}
+
+int pkt_nat_count(pkt_nat_t* t, uint64_t counts[3]) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (!counts) return nat_fail(t, "pkt_nat_count", "null counts");
+    std::vector<uint32_t> copy;
+    const uint32_t* used = t->v.used;
+    if (t->ops) {
+        const int rc = t->ops->fetch(t, nullptr, nullptr, &copy);
+        if (rc != PKT_SUCCESS) return rc;
+        used = copy.data();
+    }
+    for (uint32_t p = 0; p < 3; p++) {
+        counts[p] = 0;
+        for (uint32_t w = 0; w < t->v.W; w++) counts[p] += nat_popc(used[p * t->v.W + w]);
+    }
+    return PKT_SUCCESS;
+}
+
+int pkt_nat_export(pkt_nat_t* t, pkt_nat_record_t* records, uint64_t cap, uint64_t* n_out) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (!n_out) return nat_fail(t, "pkt_nat_export", "null n_out");
+    if (cap && !records) return nat_fail(t, "pkt_nat_export", "null records");
+    const NatView& v = t->v;
+    std::vector<uint64_t> rev_copy;
+    std::vector<uint32_t> seen_copy;
+    const uint64_t* rev = v.rev;
+    const uint32_t* seen = v.seen;
+    if (t->ops) {  // a blocking housekeeping call: the two maps come back and the records are put together here
+        const int rc = t->ops->fetch(t, &rev_copy, &seen_copy, nullptr);
+        if (rc != PKT_SUCCESS) return rc;
+        rev = rev_copy.data(), seen = seen_copy.data();
+    }
+    std::vector<pkt_nat_record_t> tmp;
+    uint64_t k = 0;
+    auto emit = [&](const pkt_nat_record_t& r) {
+        if (k < cap) {
+            if (t->ops) tmp.push_back(r); else records[k] = r;
+        }
+        k++;
+    };
+    for (uint32_t p = 0; p < 3; p++)
+        for (uint32_t e = 0; e < v.E; e++)
+            if (rev[p * v.E + e]) emit(nat_record(rev[p * v.E + e], nat_key(p, t->img.pool[e / v.nports], v.port_lo + e % v.nports), 0, seen[p * v.E + e]));
+    for (uint32_t s = 0; s < v.nstatic; s++) emit(nat_record(t->img.st_in[s], t->img.st_out[s], PKT_NAT_REC_STATIC, 0));
+    *n_out = k;
+    if (t->ops && !tmp.empty()) return t->ops->put(t, records, tmp.data(), tmp.size());
+    return PKT_SUCCESS;
+}
+
+int pkt_nat_clear(pkt_nat_t* t, void* stream) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (t->ops) return t->ops->clear(t, stream);
+    nat_host_clear(t);
+    return PKT_SUCCESS;
+}
+
+int pkt_nat_destroy(pkt_nat_t* t) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    const int rc = t->ops ? t->ops->destroy(t) : PKT_SUCCESS;
+    delete t;
+    return rc;
+}
+
+const char* pkt_nat_last_error(const pkt_nat_t* t) { return t ? t->err.c_str() : t_nat_create_err.c_str(); }
 
 // ---- pkt_frag_batch on host pointers (the CPU twin of pktgpu_frag.hip): two sequential passes over the packets with
 // the decision, the fragment header and the refusals of pktgpu_frag.hpp, which the kernels share.  The first pass

@@ -755,6 +755,14 @@ class Parser:
         (pkt_fwd_adj_t).  host=True gives the host form (pkt_fwd_host: numpy arrays in and out, no device)."""
         return Forwarder(None if host else self, adj)
 
+    def nat(self, pool, ports=(1024, 65535), slots=1 << 16, static=(), host=False):
+        """pkt_nat_create: a NAPT44 session table on this parser's device -> Nat.  `pool`: 1..64 outside IPv4 addresses
+        ("a.b.c.d" strings or 4-byte objects); `ports`: the dynamic range (lo, hi); `slots`: the forward table's size, a
+        power of two in 64..2^26 (at least twice the sessions expected); `static`: port forwards as (proto, in_addr,
+        in_port, out_addr, out_port) with proto 6 / 17 / 1 or "tcp" / "udp" / "icmp", or a numpy array of
+        schema.NAT_STATIC_DTYPE.  host=True gives the host handle (numpy arrays in and out, no device)."""
+        return Nat(None if host else self, pool, ports, slots, static)
+
     def fragment(self, batch, chain, mtu=1500, select=None, which_ip=0, only_split=False, plan_only=False,
                  out_cap=None, dst_bytes=None, hits=None, host=False, stream=None):
         """pkt_frag_batch: every packet whose L3 length is above its mtu becomes IPv4 fragments, every other packet
@@ -1828,6 +1836,193 @@ class Forwarder:
         if getattr(self, "_f", None):
             self._L.pkt_fwd_destroy(self._f)
             self._f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+(NAT_OK, NAT_SKIPPED, NAT_NO_IP, NAT_SPAN, NAT_IPV6, NAT_BAD_HDR, NAT_FRAGMENT, NAT_NO_L4, NAT_NO_SESSION, NAT_NOT_OURS,
+ NAT_EXHAUSTED, NAT_TABLE_FULL) = range(12)
+NAT_OUT, NAT_IN, NAT_NONE, NAT_STATIC, NAT_NO_WRITE = (schema.NAT_OUT, schema.NAT_IN, schema.NAT_NONE, schema.NAT_STATIC,
+                                                       schema.NAT_NO_WRITE)
+_NAT_OUT = (("status", np.uint8), ("entry", np.uint32), ("created", np.uint8))
+_NAT_PROTO = {"tcp": 6, "udp": 17, "icmp": 1}
+
+
+def _ip4(a):
+    raw = bytes(int(x) for x in a.split(".")) if isinstance(a, str) else bytes(a)
+    if len(raw) != 4:
+        raise ValueError(f"nat: an IPv4 address has 4 bytes, not {a!r}")
+    return np.frombuffer(raw, np.uint8)
+
+
+def nat_statics(static):
+    """Port forwards as a C-contiguous array of schema.NAT_STATIC_DTYPE (pkt_nat_static_t): an iterable of (proto,
+    in_addr, in_port, out_addr, out_port) tuples, or such an array, which passes through."""
+    if isinstance(static, np.ndarray):
+        if static.dtype != schema.NAT_STATIC_DTYPE:
+            raise ValueError("nat: a statics array must have schema.NAT_STATIC_DTYPE")
+        return np.ascontiguousarray(static).reshape(-1)
+    static = list(static)
+    arr = np.zeros(len(static), schema.NAT_STATIC_DTYPE)
+    for i, (proto, ia, ip, oa, op) in enumerate(static):
+        arr["proto"][i] = _NAT_PROTO.get(proto, proto)
+        arr["in_addr"][i], arr["in_port"][i], arr["out_addr"][i], arr["out_port"][i] = _ip4(ia), int(ip), _ip4(oa), int(op)
+    return arr
+
+
+class NatResult:
+    """What Nat.run gives: status (uint8 [n]: pktgpu.NAT_OK / _SKIPPED / _NO_IP / _SPAN / _IPV6 / _BAD_HDR / _FRAGMENT /
+    _NO_L4 / _NO_SESSION / _NOT_OURS / _EXHAUSTED / _TABLE_FULL), entry (uint32 [n]: p * E + e of a dynamic session,
+    NAT_STATIC | index of a static, NAT_NONE otherwise) and created (uint8 [n]: 1 for the first packet of a session the
+    call created); hits / bytes (uint64 [12]) where they were asked for.  Outputs not asked for are None."""
+
+    def __init__(self, **kw):
+        self.status = self.entry = self.created = self.hits = self.bytes = None
+        self.__dict__.update(kw)
+
+
+class Nat:
+    """pkt_nat_t: NAPT44 sessions and the translation of a parsed batch, IN PLACE (Parser.nat).  Nat(parser, ...) lives
+    on the parser's device and takes and gives device tensors; Nat(None, ...) is the host handle over numpy arrays (the
+    sequential model, no device).
+
+        nat = p.nat(["192.0.2.1"], ports=(1024, 65535), slots=1 << 20, static=[("tcp", "10.0.0.5", 80, "192.0.2.1", 80)])
+        r = nat.run(batch, chain, dir=m["action"], now=t)    # dir 0: inside -> outside, 1: outside -> inside, else skipped
+        fwd.run(batch, chain, lpm=lpm)                       # the chain columns stay valid: no second parse
+        nat.expire(t, idle=(7440, 300, 60))                  # TCP, UDP, ICMP idle times in seconds (0: never)
+    """
+
+    def __init__(self, parser, pool, ports=(1024, 65535), slots=1 << 16, static=()):
+        from . import _lib
+        self._lib = _lib
+        self._L = _lib.load()
+        self.parser = parser
+        self.pool = np.ascontiguousarray(np.stack([_ip4(a) for a in pool]) if len(pool) else np.zeros((0, 4), np.uint8))
+        self.statics = nat_statics(static)
+        self.ports = (int(ports[0]), int(ports[1]))
+        self.slots = int(slots)
+        self.nports = self.ports[1] - self.ports[0] + 1
+        self.entries = len(self.pool) * self.nports  # E
+        ns = self.statics.size
+        args = (self.pool.ctypes.data if len(self.pool) else None, len(self.pool), self.ports[0] & 0xFFFFFFFF,
+                self.ports[1] & 0xFFFFFFFF, self.slots, self.statics.ctypes.data if ns else None, ns)
+        h = ctypes.c_void_p()
+        self._t = None
+        if parser is None:
+            rc = self._L.pkt_nat_create_host(*args, ctypes.byref(h))
+            if rc != 0:
+                msg = self._L.pkt_nat_last_error(None)
+                raise ValueError(f"pkt_nat_create_host failed ({rc}): {msg.decode() if msg else ''}")
+        else:
+            parser._check(self._L.pkt_nat_create(parser._ctx, *args, ctypes.byref(h)), "pkt_nat_create")
+        self._t = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self._L.pkt_nat_last_error(self._t)
+            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+    def run(self, batch, chain, dir=NAT_OUT, now=0, select=None, which_ip=0, write=True,
+            outputs=("status", "entry", "created"), counters=None, stream=None):
+        """pkt_nat_batch: translate the batch IN PLACE -> NatResult.  `dir`: NAT_OUT / NAT_IN for every packet, or a
+        uint8 [n] array (a match action; values above 1 skip the packet).  `now`: the caller's clock in seconds.
+        `select` (uint8 [n]): a packet whose byte is 0 is skipped.  write=False: create, refresh and decide, store
+        nothing.  `outputs`: which of "status", "entry", "created" to produce.  counters: True allocates zeroed uint64
+        [12] hits and bytes and returns them; a (hits, bytes) pair passed in is accumulated into (either may be None).
+        `batch` / `chain`: the forms Lpm.lookup takes.  Device tensors for a device handle, numpy arrays for a host
+        handle.  Asynchronous on `stream`."""
+        bad = set(outputs) - {k for k, _ in _NAT_OUT}
+        if bad:
+            raise ValueError(f"nat: unknown outputs {sorted(bad)}")
+        if isinstance(batch, (tuple, list)):
+            batch = dict(zip(("slab", "offsets", "lens"), batch))
+        g = lambda k: batch.get(k)  # noqa: E731
+        host = self.parser is None
+        nc = schema.NAT_STATUS_COUNT
+        dir_all, dir_arr = (int(dir), None) if isinstance(dir, (int, np.integer)) else (0, dir)
+        if host:
+            slab = batch["slab"]
+            if write and not (isinstance(slab, np.ndarray) and slab.dtype == np.uint8 and slab.flags.c_contiguous
+                              and slab.flags.writeable):
+                raise ValueError("nat: the host handle rewrites batch['slab'] in place: a writeable C-contiguous uint8 array")
+            b, keep = _host_batch(self._lib, batch)
+            cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                    np.ascontiguousarray(chain["hdr_off"], np.uint16))
+            ch = self._lib.PktChain(*[c.ctypes.data for c in cols])
+            dir_arr = None if dir_arr is None else np.ascontiguousarray(dir_arr, np.uint8)
+            select = None if select is None else np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+            res = {k: np.zeros(b.n, dt) for k, dt in _NAT_OUT if k in outputs}
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+            zeros = lambda: np.zeros(nc, np.uint64)  # noqa: E731
+            ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
+        else:
+            torch = _torch()
+            b = self.parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
+            ch = self.parser._chain(chain)
+            for a in (dir_arr, select):
+                assert a is None or (a.is_cuda and a.dtype == torch.uint8 and a.is_contiguous() and a.numel() >= b.n)
+            dev = self.parser.torch_device
+            res = {k: torch.empty(b.n, dtype=_tdtype(dt), device=dev) for k, dt in _NAT_OUT if k in outputs}
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+            zeros = lambda: torch.zeros(nc, dtype=torch.uint64, device=dev)  # noqa: E731
+            ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
+        hits, nbytes = (zeros(), zeros()) if counters is True else (None, None) if not counters else counters
+        for name, c in (("hits", hits), ("bytes", nbytes)):
+            if c is not None:
+                assert ok(c), f"nat: {name} is a contiguous uint64 [{nc}] array"
+                res[name] = c
+        self._check(self._L.pkt_nat_batch(self._t, ctypes.byref(b), ctypes.byref(ch), int(which_ip),
+                                          0 if write else schema.NAT_NO_WRITE, dir_all & 0xFFFFFFFF, ptr(dir_arr), ptr(select),
+                                          int(now) & 0xFFFFFFFF, *[ptr(res.get(k)) for k, _ in _NAT_OUT], ptr(hits),
+                                          ptr(nbytes), None if host else self.parser._stream(stream)), "pkt_nat_batch")
+        return NatResult(**res)
+
+    def expire(self, now, idle):
+        """pkt_nat_expire (blocking): remove the dynamic sessions of protocol p (TCP, UDP, ICMP) with idle[p] != 0 and
+        last_seen + idle[p] <= now -> how many were removed.  `idle`: one number for all three, or three."""
+        idle = [int(idle)] * 3 if isinstance(idle, (int, np.integer)) else [int(x) for x in idle]
+        if len(idle) != 3:
+            raise ValueError("nat: idle is one number or three (TCP, UDP, ICMP)")
+        arr = (ctypes.c_uint32 * 3)(*idle)
+        gone = ctypes.c_uint64()
+        self._check(self._L.pkt_nat_expire(self._t, int(now) & 0xFFFFFFFF, arr, ctypes.byref(gone)), "pkt_nat_expire")
+        return gone.value
+
+    def count(self):
+        """pkt_nat_count (blocking) -> the dynamic sessions per protocol (TCP, UDP, ICMP)."""
+        c = (ctypes.c_uint64 * 3)()
+        self._check(self._L.pkt_nat_count(self._t, c), "pkt_nat_count")
+        return tuple(int(x) for x in c)
+
+    def sessions(self):
+        """pkt_nat_export (blocking) -> a numpy array of schema.NAT_RECORD_DTYPE: the dynamic sessions in ascending
+        (protocol index, pool entry), then the statics (flags = schema.NAT_REC_STATIC) in the order given."""
+        cap = sum(self.count()) + self.statics.size
+        n = ctypes.c_uint64()
+        if self.parser is None:
+            rec = np.zeros(cap, schema.NAT_RECORD_DTYPE)
+            self._check(self._L.pkt_nat_export(self._t, rec.ctypes.data if cap else None, cap, ctypes.byref(n)),
+                        "pkt_nat_export")
+        else:
+            torch = _torch()
+            t = torch.zeros(max(cap, 1) * schema.NAT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=self.parser.torch_device)
+            self._check(self._L.pkt_nat_export(self._t, t.data_ptr(), cap, ctypes.byref(n)), "pkt_nat_export")
+            rec = t.cpu().numpy()[:cap * schema.NAT_RECORD_DTYPE.itemsize].view(schema.NAT_RECORD_DTYPE)
+        return rec[:min(cap, n.value)].copy()
+
+    def clear(self, stream=None):
+        """pkt_nat_clear: no dynamic session, cursors 0; the statics stay.  Asynchronous on `stream`."""
+        self._check(self._L.pkt_nat_clear(self._t, None if self.parser is None else self.parser._stream(stream)),
+                    "pkt_nat_clear")
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self._L.pkt_nat_destroy(self._t)
+            self._t = None
 
     def __del__(self):
         try:

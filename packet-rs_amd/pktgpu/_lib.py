@@ -103,6 +103,17 @@ class PktIcmpCfg(ctypes.Structure):
                 ("max6", ctypes.c_uint16), ("ident", ctypes.c_uint16), ("ttl", ctypes.c_uint8), ("tos", ctypes.c_uint8)]
 
 
+class PktNatStatic(ctypes.Structure):
+    _fields_ = [("in_addr", ctypes.c_uint8 * 4), ("out_addr", ctypes.c_uint8 * 4), ("in_port", ctypes.c_uint16),
+                ("out_port", ctypes.c_uint16), ("proto", ctypes.c_uint8), ("zero", ctypes.c_uint8 * 3)]
+
+
+class PktNatRecord(ctypes.Structure):
+    _fields_ = [("in_addr", ctypes.c_uint8 * 4), ("out_addr", ctypes.c_uint8 * 4), ("in_port", ctypes.c_uint16),
+                ("out_port", ctypes.c_uint16), ("proto", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("zero", ctypes.c_uint16), ("last_seen", ctypes.c_uint32)]
+
+
 class PktFwdAdj(ctypes.Structure):
     _fields_ = [("dmac", ctypes.c_uint8 * 6), ("smac", ctypes.c_uint8 * 6), ("port", ctypes.c_uint32),
                 ("mtu", ctypes.c_uint16), ("action", ctypes.c_uint8), ("zero", ctypes.c_uint8)]
@@ -311,6 +322,21 @@ SIGNATURES = {
                                          ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
                                          ctypes.POINTER(PktChain), _P, ctypes.POINTER(ctypes.c_uint64),
                                          ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_sizeof_nat_static": (ctypes.c_size_t, []),
+    "pkt_sizeof_nat_record": (ctypes.c_size_t, []),
+    "pkt_nat_create": (ctypes.c_int, [_P, _P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, _P,
+                                      ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "pkt_nat_create_host": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, _P,
+                                           ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "pkt_nat_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                     ctypes.c_uint32, ctypes.c_uint32, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "pkt_nat_expire": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                      ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_nat_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_nat_export": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_nat_clear": (ctypes.c_int, [_P, _P]),
+    "pkt_nat_destroy": (ctypes.c_int, [_P]),
+    "pkt_nat_last_error": (ctypes.c_char_p, [_P]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -395,7 +421,9 @@ def load():
             or L.pkt_sizeof_match_rule() != ctypes.sizeof(PktMatchRule) \
             or L.pkt_sizeof_lpm_route() != ctypes.sizeof(PktLpmRoute) \
             or L.pkt_sizeof_scan_pattern() != ctypes.sizeof(PktScanPattern) \
-            or L.pkt_sizeof_fwd_adj() != ctypes.sizeof(PktFwdAdj):
+            or L.pkt_sizeof_fwd_adj() != ctypes.sizeof(PktFwdAdj) \
+            or L.pkt_sizeof_nat_static() != ctypes.sizeof(PktNatStatic) \
+            or L.pkt_sizeof_nat_record() != ctypes.sizeof(PktNatRecord):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L
     return L

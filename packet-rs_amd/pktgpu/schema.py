@@ -59,6 +59,20 @@ FWD_KEEP_L2 = 1        # flags: no Ether entry is looked for, no MAC is written
 FWD_NO_WRITE = 2       # flags: decide everything, store nothing into the slab
 FWD_MAX_ADJ = 1 << 20
 
+# pkt_nat_* (NAPT44 sessions and translation)
+(NAT_OK, NAT_SKIPPED, NAT_NO_IP, NAT_SPAN, NAT_IPV6, NAT_BAD_HDR, NAT_FRAGMENT, NAT_NO_L4, NAT_NO_SESSION, NAT_NOT_OURS,
+ NAT_EXHAUSTED, NAT_TABLE_FULL) = range(12)
+NAT_STATUS = ["OK", "SKIPPED", "NO_IP", "SPAN", "IPV6", "BAD_HDR", "FRAGMENT", "NO_L4", "NO_SESSION", "NOT_OURS",
+              "EXHAUSTED", "TABLE_FULL"]
+NAT_STATUS_COUNT = 12
+NAT_OUT, NAT_IN = 0, 1
+NAT_NO_WRITE = 1         # flags: create, refresh and decide, store nothing into the slab
+NAT_NONE = 0xFFFFFFFF    # entry[i] of a packet that is not OK
+NAT_STATIC = 0x80000000  # entry[i] = NAT_STATIC | the static's index
+NAT_REC_STATIC = 1
+NAT_MAX_ADDR, NAT_MAX_STATIC = 64, 4096
+NAT_PROTOS = (6, 17, 1)  # protocol index p -> IP protocol
+
 # pkt_frag_* (IPv4 fragmentation to a per-packet MTU)
 (FRAG_FITS, FRAG_SPLIT, FRAG_SKIPPED, FRAG_NO_IP, FRAG_SPAN, FRAG_IPV6, FRAG_BAD_HDR, FRAG_TRUNC, FRAG_DF,
  FRAG_MTU) = range(10)
@@ -133,6 +147,13 @@ SCAN_PATTERN_DTYPE = np.dtype([("off", np.uint32), ("len", np.uint16), ("flags",
 # pkt_fwd_adj_t as a numpy record
 FWD_ADJ_DTYPE = np.dtype([("dmac", np.uint8, 6), ("smac", np.uint8, 6), ("port", np.uint32), ("mtu", np.uint16),
                           ("action", np.uint8), ("zero", np.uint8)])
+
+# pkt_nat_static_t and pkt_nat_record_t as numpy records (addresses: wire bytes; ports: host order)
+NAT_STATIC_DTYPE = np.dtype([("in_addr", np.uint8, 4), ("out_addr", np.uint8, 4), ("in_port", np.uint16),
+                             ("out_port", np.uint16), ("proto", np.uint8), ("zero", np.uint8, 3)])
+NAT_RECORD_DTYPE = np.dtype([("in_addr", np.uint8, 4), ("out_addr", np.uint8, 4), ("in_port", np.uint16),
+                             ("out_port", np.uint16), ("proto", np.uint8), ("flags", np.uint8), ("zero", np.uint16),
+                             ("last_seen", np.uint32)])
 
 # pkt_hdr_type_t -> Header::name() of the reference (headers.rs:529-827)
 HDR_NAMES = [
