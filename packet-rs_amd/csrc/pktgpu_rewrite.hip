@@ -393,10 +393,11 @@ __device__ __forceinline__ void load_src_chunk(const BatchRef& b, uint64_t last1
         return;
     }
     // source of destination byte ca: B = ca - d + s (below 0 only for bytes before the packet,
-    // which are not stored)
+    // which are not stored: a packet in the slab's first 16 bytes going to a higher alignment).  Then
+    // A = -16: the second load is the slab's first chunk, the first one is read anywhere valid
     const int64_t B = (int64_t)(ca - d) + (int64_t)s;
     const int64_t A = B & ~(int64_t)15;
-    uint64_t a0 = A < 0 ? 0 : (uint64_t)A, a1 = a0 + 16;
+    uint64_t a0 = A < 0 ? 0 : (uint64_t)A, a1 = (uint64_t)(A + 16);
     a0 = a0 > last16 ? last16 : a0;
     a1 = a1 > last16 ? last16 : a1;
     const uint4 v0 = *reinterpret_cast<const uint4*>(b.slab + a0);

@@ -643,6 +643,34 @@ def test_to_vec_dst_layouts_in_order_vs_oracle(P, layout):
     assert (o[mask] == 0xEE).all()
 
 
+@pytest.mark.parametrize("s0", [0, 3, 15])
+def test_to_vec_first_packet_in_the_slabs_first_chunk_to_every_alignment(P, s0):
+    """A packet that starts in the slab's first 16 bytes (at s0) written to every destination alignment: above
+    s0 the source of the first destination chunk begins before the slab, where nothing may be read and the
+    packet's bytes must not shift.  Every to_vec equals the oracle's and no other destination byte changes."""
+    pk = [bytes(p.to_vec()) for p in gen.reference_22_packets()[:3]]
+    lens = np.array([len(x) for x in pk], np.uint64)
+    offs = (np.concatenate([[0], np.cumsum(lens + np.uint64(16))[:-1]]) + s0).astype(np.uint64)
+    buf = np.zeros(int(offs[-1] + lens[-1]), np.uint8)
+    for i, x in enumerate(pk):
+        buf[int(offs[i]):int(offs[i]) + len(x)] = np.frombuffer(x, np.uint8)
+    ds, do, dl = dev(buf), dev(offs), dev(lens.astype(np.uint32))
+    res = P.parse(ds, offsets=do, lens=dl, columns=["chain"])
+    want = [oracle.slow_parse_to_vec(x) for x in pk]
+    for al in range(16):
+        doff = (np.arange(3, dtype=np.uint64) * np.uint64(512) + np.uint64(al))
+        dst = torch.full((3 * 512,), 0xEE, dtype=torch.uint8, device="cuda")
+        out, ln = P.to_vec(ds, res, offsets=do, lens=dl, dst=dst, dst_offsets=dev(doff))
+        torch.cuda.synchronize()
+        o, ln = out.cpu().numpy(), ln.cpu().numpy()
+        mask = np.ones(o.size, bool)
+        for i, w in enumerate(want):
+            a = int(doff[i])
+            assert int(ln[i]) == len(w) and o[a:a + len(w)].tobytes() == w, (al, i)
+            mask[a:a + len(w)] = False
+        assert (o[mask] == 0xEE).all(), al
+
+
 def test_to_vec_capture_empty_last_record_at_a_window_start(P):
     """A capture-layout batch whose last record is empty and starts exactly at a 4 KiB boundary: an
     empty record sends the batch to to_vec_kernel (the window path would have no window to write its
