@@ -458,6 +458,59 @@ class Parser {
         return t;
     }
 
+    // A tunnel table on this context's device (pkt_tunnel_create): VXLAN, GRE and IP-in-IP entries that tunnel_encap
+    // puts packets into and tunnel_decap takes them out of.  Read-only: calls on several streams share it.  The caller
+    // destroys it with pkt_tunnel_destroy after the calls queued on it.
+    pkt_tunnel_t* tunnels(const std::vector<pkt_tunnel_entry_t>& entries) {
+        pkt_tunnel_t* t = nullptr;
+        check(pkt_tunnel_create(ctx_, entries.data(), (uint32_t)entries.size(), &t), ctx_, "pkt_tunnel_create");
+        return t;
+    }
+
+    // Encapsulation of a parsed batch (pkt_tunnel_encap_batch): packet i goes into entry tunnel[i] (or tunnel_all when
+    // `tunnel` is NULL: pkt_lpm_lookup_batch's nexthop or pkt_fwd_batch's adj_index as they are); every packet that may
+    // gives one output with correct outer lengths and checksums, packed into dst as fragment packs its outputs, and
+    // out_chain holds the outer rows and the source's with their offsets moved.  entropy[i] (NULL: none) spreads
+    // VXLAN's UDP source port; the outer IPv4 identification of output q is (ident + q) & 0xFFFF.  With
+    // PKT_TUN_NO_WRITE in `flags` only status / out_index / hits and the totals are produced.  Waits for the totals.
+    FragTotals tunnel_encap(const pkt_tunnel_t* t, const pkt_batch_t& b, const pkt_chain_t& chain, const uint32_t* tunnel,
+                            uint32_t tunnel_all, const uint32_t* entropy, uint32_t ident, uint8_t* dst, uint64_t dst_len,
+                            uint64_t out_cap, uint64_t* out_off, uint32_t* out_len, const pkt_chain_t* out_chain = nullptr,
+                            uint32_t* src_index = nullptr, uint8_t* status = nullptr, uint32_t* out_index = nullptr,
+                            const uint8_t* select = nullptr, uint32_t which_ip = 0, uint32_t flags = 0,
+                            uint64_t* hits = nullptr, hipStream_t s = nullptr) {
+        FragTotals r;
+        const int rc = pkt_tunnel_encap_batch(ctx_, &b, &chain, which_ip, flags, t, tunnel, tunnel_all, entropy, ident, select,
+                                              status, out_index, dst, dst_len, out_cap, out_off, out_len, src_index, out_chain,
+                                              hits, &r.bytes, &r.n_out, s);
+        if (rc == PKT_ERR_INVALID_ARG && (r.n_out || r.bytes)) {
+            r.fits = false;
+            return r;
+        }
+        check(rc, ctx_, "pkt_tunnel_encap_batch");
+        return r;
+    }
+
+    // Decapsulation (pkt_tunnel_decap_batch), the inverse: every packet whose which_ip-th IP entry is the outer header
+    // of a tunnel of the table gives its inner packet; tunnel_out[i] is the matched entry (PKT_TUN_NONE: none).  Outer
+    // fragments are refused (reassemble first) and no checksum is verified (l4_checksum first).
+    FragTotals tunnel_decap(const pkt_tunnel_t* t, const pkt_batch_t& b, const pkt_chain_t& chain, uint8_t* dst,
+                            uint64_t dst_len, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len,
+                            const pkt_chain_t* out_chain = nullptr, uint32_t* src_index = nullptr, uint8_t* status = nullptr,
+                            uint32_t* out_index = nullptr, uint32_t* tunnel_out = nullptr, const uint8_t* select = nullptr,
+                            uint32_t which_ip = 0, uint32_t flags = 0, uint64_t* hits = nullptr, hipStream_t s = nullptr) {
+        FragTotals r;
+        const int rc = pkt_tunnel_decap_batch(ctx_, &b, &chain, which_ip, flags, t, select, status, out_index, tunnel_out, dst,
+                                              dst_len, out_cap, out_off, out_len, src_index, out_chain, hits, &r.bytes, &r.n_out,
+                                              s);
+        if (rc == PKT_ERR_INVALID_ARG && (r.n_out || r.bytes)) {
+            r.fits = false;
+            return r;
+        }
+        check(rc, ctx_, "pkt_tunnel_decap_batch");
+        return r;
+    }
+
     // IPv4 reassembly of a batch's fragments (pkt_reasm_batch), the inverse of fragment: the fragments are grouped by
     // (src, dst, protocol, identification) and every datagram that is complete in this batch is joined into one packet
     // at the place of its last-arriving member; packets that are no fragments go through whole.  dst, out_off /

@@ -1252,8 +1252,8 @@ int pkt_fwd_host(const pkt_fwd_adj_t *adj, uint32_t nadj, const pkt_batch_t *bat
  * ordered by (i, j): source order, then fragment order; the result is exact and the same from run to run.
  * A FITS output is the packet's bytes [0, len_i) verbatim, trailing padding included.  Fragment j of a SPLIT packet is
  *  - the source bytes [0, ip_off) verbatim: the L2 prefix and any outer headers.  When which_ip selects an inner
- *    header the outer headers' length fields (outer IP total length, UDP length) are NOT corrected: that is the
- *    caller's to fix (pkt_set_fields_csum);
+ *    header the outer headers' length fields (outer IP total length, UDP length) are NOT corrected: encapsulate
+ *    first (pkt_tunnel_encap_batch, below, sets them) and fragment the outer datagram;
  *  - the 20-byte IP header, the source's with bytes 2..3 = 20 + the slice's length; bytes 6..7 = (w & 0xC000) | MF |
  *    (o + j * per / 8), MF = 0x2000 for j < k - 1 and w & 0x2000 for the last fragment (a fragment of a fragment keeps
  *    its more-fragments bit); bytes 10..11 = HC', updated incrementally over the two changed words, pkt_fwd_batch's
@@ -1300,7 +1300,9 @@ int pkt_fwd_host(const pkt_fwd_adj_t *adj, uint32_t nadj, const pkt_batch_t *bat
  * for dst, hits, out_off and mtu and are waived for the slab.
  * Out of scope: ICMP fragmentation-needed / packet-too-big generation (pkt_icmp_err_batch, below: PKT_FRAG_DF and
  * PKT_FRAG_IPV6 are its inputs);
- * reassembly (pkt_reasm_batch, below); IPv4 options; fixing outer tunnel lengths. */
+ * reassembly (pkt_reasm_batch, below); IPv4 options.  With which_ip on an inner header the outer tunnel's length fields
+ * are left as they are: to send tunnelled packets over a smaller MTU, fragment the inner packets first and encapsulate
+ * the fragments, or encapsulate first and fragment the OUTER datagram (pkt_tunnel_encap_batch, below, sets its lengths). */
 typedef enum pkt_frag_status {
     PKT_FRAG_FITS    = 0, /* one output: the packet, whole */
     PKT_FRAG_SPLIT   = 1, /* nfrag >= 2 outputs */
@@ -1379,7 +1381,7 @@ int pkt_frag_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t w
  *    twice, exactly as pkt_frag_batch's fragment header: a checksum that was wrong stays wrong by the same amount);
  *  - then every member's payload, its own bytes [ip_off_m + 20, ip_off_m + L_m), at ip_off0 + 20 + s_m.
  * Source bytes past a member's ip_off + L go nowhere.  When which_ip selects an inner header the outer headers' length
- * fields are NOT corrected (pkt_frag_batch's caveat).
+ * fields are NOT corrected (pkt_frag_batch's caveat): reassemble the outer fragments, then pkt_tunnel_decap_batch.
  * Layout of dst, out_off / out_len, the 16-byte rounding with zero fill, the empty tail up to out_cap (out_off 0,
  * out_len 0, src_index PKT_REASM_NONE, nfrag 0, out_chain->n_hdrs 0), *bytes_out_total, *n_out, hits (device
  * uint64_t[PKT_REASM_STATUS_COUNT], ADDED to, exactly n per call), the overflow return (PKT_ERR_INVALID_ARG with both
@@ -1828,6 +1830,237 @@ int pkt_nat_export(pkt_nat_t *nat, pkt_nat_record_t *records, uint64_t cap, uint
 int pkt_nat_clear(pkt_nat_t *nat, void *stream);
 int pkt_nat_destroy(pkt_nat_t *nat);
 const char *pkt_nat_last_error(const pkt_nat_t *nat);
+
+/* ---- pkt_tunnel_*: VXLAN, GRE and IP-in-IP encapsulation and decapsulation of a batch ----
+ * What an overlay or edge router does before and after everything else: put every packet of a parsed batch into the
+ * tunnel a table entry describes, or take the packets of terminated tunnels out again.  The outputs are packed into a
+ * second slab exactly as pkt_frag_batch packs its own, with the chain columns the following calls need.  The wire
+ * formats are RFC 7348 (VXLAN), RFC 2784 / 2890 (GRE, version 0, optional key) and RFC 2003 / 2473 (IP in IP); the
+ * reference's builders (utils.rs create_vxlan_packet, create_gre_packet, create_ipv4ip_packet, create_ipv6ip_packet)
+ * give the same bytes but for the outer IPv4 checksum they leave stale (Q9) and the 0xFFFF they store as the IPv6 UDP
+ * checksum.
+ *
+ * The table.  pkt_tunnel_create: blocking, and the only allocating call; 1..PKT_TUN_MAX_ENTRIES entries.  An entry:
+ *    kind    PKT_TUN_VXLAN: outer Ether / IP / UDP (destination 4789) / VXLAN around the whole source frame;
+ *            PKT_TUN_GRE: outer IP / GRE around the source's IP packet; PKT_TUN_IPIP: outer IP around it.
+ *    ipver   the outer IP version, 4 or 6; src / dst: the outer addresses, wire bytes, IPv4 in the first 4.
+ *    ttl     the outer ttl / hop limit, 0 = 64; tos: the outer tos / traffic class.
+ *    id      the VNI (at most 2^24 - 1), or the GRE key with PKT_TUN_F_KEY; otherwise ignored.
+ *    sport_lo / sport_hi  VXLAN's UDP source port range (ignored by the other kinds, the order is still checked).
+ *    eth_dst / eth_src    VXLAN's outer MACs; pkt_fwd_batch over the output rewrites them, so they may be zero.
+ *    flags   PKT_TUN_F_KEY: GRE carries `id` as its key.  PKT_TUN_F_DF: the outer IPv4 header has DF set.
+ *            PKT_TUN_F_INHERIT_TOS: the outer tos / traffic class is the inner IP header's (IPv4 byte 1, the IPv6 traffic
+ *            class); for VXLAN that of the chain's first IPv4 / IPv6 entry if its first two bytes lie inside the packet,
+ *            else the entry's tos.  PKT_TUN_F_UDP_CSUM: the outer UDP checksum is computed; without it an IPv4 outer
+ *            stores 0 (RFC 7348) and an IPv6 outer stores 0 as well (RFC 6935 zero-checksum mode for tunnels).
+ *            PKT_TUN_F_ANY_REMOTE: decap matches any outer source address.
+ * On the host, create builds the decap lookup: open addressing with linear probing over the entries' keys (kind,
+ * ipver, GRE key present, local = src, remote = dst or the wildcard with ANY_REMOTE, id as matched: the VNI, the key,
+ * else 0), at least twice as many slots as entries, read-only afterwards: encap and decap calls on several streams
+ * share a handle.  PKT_ERR_INVALID_ARG with a text starting "pkt_tunnel" (pkt_ctx_last_error for pkt_tunnel_create,
+ * pkt_tunnel_last_error(NULL) on the calling thread for pkt_tunnel_create_host): NULL entries; a count of 0 or above
+ * PKT_TUN_MAX_ENTRIES; an unknown kind; an ipver that is neither 4 nor 6; unknown flag bits; a VNI above 2^24 - 1;
+ * sport_lo > sport_hi; KEY on an entry that is not GRE; UDP_CSUM on an entry that is not VXLAN; a non-zero `zero`; two
+ * entries with the same decap key.  pkt_tunnel_create_host gives the same handle on host memory for the _host calls.
+ *
+ * pkt_tunnel_encap_batch, per source packet i: the first test that applies gives status[i].  t = tunnel ? tunnel[i] :
+ * tunnel_all (pkt_lpm_lookup_batch's nexthop or pkt_fwd_batch's adj_index / port as they are); E = entry t.
+ *  1. select != NULL && select[i] == 0: PKT_TUNE_SKIPPED.
+ *  2. t >= the table's size: PKT_TUNE_NO_TUNNEL.
+ *  Steps 3 to 7 are for GRE and IPIP alone (VXLAN wraps the frame whatever it holds; which_ip is not used):
+ *  3. The IP entry is found exactly as in pkt_fwd_batch step 2 (which_ip, PKT_FLOW_LAST included, over min(n_hdrs,
+ *     PKT_MAX_HDRS) entries).  None: PKT_TUNE_NO_IP.  Its 20 / 40 bytes not inside the packet's length (under the
+ *     pkt_batch_t clamp rules): PKT_TUNE_SPAN.  P = ip_off.
+ *  4. The IP entry is not entry 0 and the entry just before it is neither Ether nor VLAN nor MPLS: PKT_TUNE_BAD_L2.
+ *  5. That entry is Ether or VLAN and ip_off < 2 (only a forged chain gives that): PKT_TUNE_SPAN.
+ *  6. IPv4: byte 0 != 0x45 or L = bytes 2..3 < 20; IPv6: byte 0 >> 4 != 6 (L = 40 + bytes 4..5): PKT_TUNE_BAD_HDR.
+ *  7. ip_off + L > the packet's length: PKT_TUNE_TRUNC.
+ *  8. The outer IP length field would pass 65535: PKT_TUNE_TOO_BIG.  VXLAN: 36 + len under IPv4, 16 + len under IPv6;
+ *     GRE / IPIP: 20 + G + L under IPv4, G + L under IPv6, G = 0 (IPIP), 4 or 8 (GRE without / with the key).
+ *  9. min(n_hdrs, PKT_MAX_HDRS) plus the added rows (VXLAN 4, IPIP 1, GRE 2 or 3) exceeds PKT_MAX_HDRS: PKT_TUNE_DEPTH.
+ * 10. PKT_TUNE_OK: one output.
+ * The output of an OK packet:
+ *  - VXLAN, 50 / 70 + len bytes: Ether (eth_dst, eth_src, 0x0800 / 0x86DD), the outer IP, UDP (source port sport_lo +
+ *    entropy[i] % (sport_hi - sport_lo + 1), sport_lo without `entropy`; destination 4789; length 16 + len; checksum),
+ *    VXLAN (08 00 00 00, VNI, 00), then the source packet's bytes [0, len).
+ *  - GRE / IPIP, P + H + G + L bytes: the source's [0, P) verbatim, the two bytes before P set to the outer version's
+ *    ethertype when the entry before the IP entry is Ether or VLAN (MPLS has none to set); the outer IP; GRE (flags
+ *    0x2000 with the key else 0, protocol 0x0800 / 0x86DD by the inner version, then the key); the inner bytes [P, P +
+ *    L).  Source bytes past P + L (Ethernet padding) go nowhere, as in pkt_frag_batch.
+ *  - Outer IPv4: 45, tos, the total length, identification (ident + q) & 0xFFFF with q the output's index
+ *    (pkt_icmp_err_batch's rule), bytes 6..7 = 0x4000 with DF else 0, ttl, protocol 17 / 47 / 4 or 41 by the inner
+ *    version, the RFC 1071 checksum of the 20 bytes, src, dst.  The checksum is the correct fold (as in
+ *    pkt_icmp_err_batch); Packet::ipv4_checksum gives the same value except where its single fold drops a carry.
+ *  - Outer IPv6: version 6, traffic class tos, flow label 0, the payload length, next header as above, hop limit, src, dst.
+ *  - The UDP checksum with PKT_TUN_F_UDP_CSUM: RFC 1071 over the pseudo-header and the whole datagram; a computed 0 is
+ *    stored as 0xFFFF: what pkt_l4_checksum_batch (which = 0) calls PKT_L4_OK, and PKT_L4_UNCHECKED without the flag.
+ * out_chain: VXLAN: (Ether, 0), (IPv4 / IPv6, 14), (UDP, 14 + H), (VXLAN, 22 + H), then the source's rows with hdr_off
+ * + 50 / 70.  GRE / IPIP: the source's rows before the IP entry as they are, (IPv4 / IPv6, P), for GRE (GRE, P + H) and
+ * with the key (GRE_KEY, P + H + 4) (the reference's list order), then the source's rows from the IP entry on with
+ * hdr_off + H + G.  That is what a parse of the output gives for a source that starts with an Ether entry, so
+ * pkt_fwd_batch with which_ip = 0 (it routes on the outer header), pkt_frag_batch (it splits the OUTER datagram: encap
+ * first, then fragment, is the order in which no outer length is left to fix), pkt_l4_checksum_batch,
+ * pkt_flow_key_batch, pkt_dispatch_batch and pkt_pcap_write take the result with no second parse.
+ *
+ * pkt_tunnel_decap_batch, per source packet i: the first test that applies gives status[i].
+ *  1. select != NULL && select[i] == 0: PKT_TUND_SKIPPED.
+ *  2. The outer IP entry is the which_ip-th IP entry (step 3 above).  None: PKT_TUND_NO_IP.
+ *  3. Its H = 20 / 40 bytes not inside the packet's length: PKT_TUND_SPAN.  A = ip_off + H.
+ *  4. IPv4 byte 0 != 0x45; IPv6 byte 0 >> 4 != 6: PKT_TUND_BAD_HDR.
+ *  5. IPv4 with (bytes 6..7 & 0x3FFF) != 0, any fragment: PKT_TUND_FRAGMENT (pkt_reasm_batch first).
+ *  6. The kind is read from the chain entries behind the IP entry: (UDP, A) and (VXLAN, A + 8): VXLAN, T = 16; (GRE,
+ *     A): GRE, T = 4; (IPv4 / IPv6, A): IPIP, T = 0.  Anything else, a differing hdr_off included: PKT_TUND_NOT_TUNNEL.
+ *  7. A + T > the packet's length: PKT_TUND_SPAN.  Lo = IPv4 bytes 2..3, or 40 + IPv6 bytes 4..5.
+ *  8. VXLAN: the UDP length != Lo - H: PKT_TUND_BAD_HDR.  GRE: byte 0 & 0xD0 (checksum, routing, sequence), byte 1 & 7
+ *     (version), a protocol that is neither 0x0800 nor 0x86DD, or a GRE_CHKSUM_OFFSET / GRE_SEQUENCE_NUM entry among
+ *     the two entries behind the GRE entry: PKT_TUND_BAD_GRE.  GRE with the key bit: T = 8, and A + 8 > the length:
+ *     PKT_TUND_SPAN.
+ *  9. The lookup: (kind, outer version, key present, local = the outer destination, remote = the outer source, id =
+ *     the VNI / the key / 0), the exact key first, then the ANY_REMOTE key.  No entry: PKT_TUND_NO_MATCH.
+ * 10. ip_off + Lo > the packet's length: PKT_TUND_TRUNC.
+ * 11. I = Lo - H - T (0 if that is negative).  VXLAN: no chain entry behind the VXLAN entry, or I < 14; GRE / IPIP: I <
+ *     20 / 40 by the inner version (GRE's protocol, IPIP's chain entry): PKT_TUND_NO_INNER.
+ * 12. PKT_TUND_OK: one output.  VXLAN: the source's [A + 16, ip_off + Lo), I bytes; out_chain = the source's rows behind
+ *     the VXLAN entry with hdr_off - (A + 16).  GRE / IPIP: the source's [0, ip_off) with the two bytes before ip_off set
+ *     to the inner version's ethertype when the entry before the IP entry is Ether or VLAN, then [A + T, ip_off + Lo);
+ *     out_chain = the rows before the IP entry, then the rows behind the outer ones (IP, GRE, GRE_KEY) with hdr_off -
+ *     (H + T).  Rows whose hdr_off a forged chain put below what is subtracted wrap modulo 2^16.
+ * tunnel_out[i] = the matched entry from step 9 on, PKT_TUN_NONE before.  Checksums are NOT verified:
+ * pkt_l4_checksum_batch before this call if that is wanted.
+ *
+ * Both calls.  Outputs are in source order, exact and the same from run to run.  Per source packet: status[i] and
+ * out_index[i] (PKT_TUN_NONE without an output).  dst, out_off, out_len, src_index, out_chain, the layout rule
+ * (out_off[q + 1] = out_off[q] + round_up(out_len[q], 16), the rounded tail zeros), the empty tail [*n_out, out_cap),
+ * PKT_TUN_NO_WRITE (the sizing pass: only status, out_index, tunnel_out, hits and the totals), the overflow return with
+ * both totals set and decided on the device, and _async / _result with one call in flight per ctx AND entry (an encap
+ * and a decap may be in flight together) are pkt_frag_batch's, word for word.  status, out_index, tunnel_out,
+ * src_index, hits, out_chain and each of its columns may be NULL.  Chain columns that are not a parse of the batch give
+ * a status or unspecified output bytes, never an access outside [slab, slab + round_up(slab_len, 16)).
+ * hits: device uint64_t[PKT_TUNE_STATUS_COUNT / PKT_TUND_STATUS_COUNT], 8-byte aligned, ADDED to; every call adds exactly n.
+ *  - PKT_ERR_INVALID_ARG before any launch, with a text starting "pkt_tunnel" in pkt_ctx_last_error: pkt_frag_batch's
+ *    batch, slab, chain, which_ip, flag, alignment (dst 16, hits 8, out_off 8) and capacity rules; a NULL table; a host
+ *    handle (a device handle for the _host calls); a table of another device; tunnel / entropy / tunnel_out not 4-byte
+ *    aligned; a second call of the same entry on the ctx before its _result.  n == 0 succeeds with both totals 0.
+ *  - Scratch lives in the ctx and grows on demand.
+ *  - On the device, three launches: a decision kernel (a lane owns a source packet: the chain, the entry by four
+ *    16-byte loads, the header bytes the tests need by the aligned 16-byte chunks that hold them, for decap the lookup,
+ *    a 32-byte plan; per tile of 256 the outputs and rounded bytes; per-status counts merged per block in LDS), the
+ *    one-block scan pkt_frag_batch uses, and one build kernel for both calls (a wave walks the 16-byte chunks of its 64
+ *    sources' outputs together; each chunk is built in registers from the prefix, the header words and the two aligned
+ *    source chunks that hold its payload bytes, and stored whole; with UDP_CSUM the payload's 16-bit words are summed
+ *    chunk by chunk into the output's LDS word and the chunk that holds the checksum is stored once the wave's sums
+ *    are complete; the lane writes its output's out_chain rows).  No lane waits for another; no global atomics but hits.
+ * pkt_tunnel_encap_host / _decap_host are the same operations on HOST pointers with a pkt_tunnel_create_host handle: no
+ * ctx, no device; the slab's alignment rule is waived.
+ * Out of scope: Geneve; NVGRE / GRE transparent bridging (the parser does not walk 0x6558); MPLS push; IPv6 extension
+ * headers and IPv4 options; the ECN decapsulation rules of RFC 6040; outer checksum verification; per-tunnel counters
+ * (a bincount of tunnel_out). */
+typedef struct pkt_tunnel pkt_tunnel_t;
+typedef struct pkt_tunnel_entry {  /* 64 bytes */
+    uint8_t  kind;                 /* pkt_tunnel_kind_t */
+    uint8_t  ipver;                /* 4 or 6 */
+    uint8_t  ttl;                  /* 0 = 64 */
+    uint8_t  tos;
+    uint32_t flags;                /* PKT_TUN_F_* */
+    uint32_t id;                   /* the VNI or the GRE key */
+    uint16_t sport_lo;
+    uint16_t sport_hi;
+    uint8_t  src[16];              /* wire bytes, IPv4 in the first 4 */
+    uint8_t  dst[16];
+    uint8_t  eth_dst[6];
+    uint8_t  eth_src[6];
+    uint32_t zero;
+} pkt_tunnel_entry_t;
+typedef enum pkt_tunnel_kind {
+    PKT_TUN_VXLAN = 0,
+    PKT_TUN_GRE   = 1,
+    PKT_TUN_IPIP  = 2
+} pkt_tunnel_kind_t;
+typedef enum pkt_tune_status {
+    PKT_TUNE_OK        = 0,  /* one output */
+    PKT_TUNE_SKIPPED   = 1,  /* select[i] == 0 */
+    PKT_TUNE_NO_TUNNEL = 2,  /* the index is at or above the table's size */
+    PKT_TUNE_NO_IP     = 3,  /* GRE / IPIP: the chain has no such IP entry */
+    PKT_TUNE_SPAN      = 4,  /* its bytes are not inside the packet */
+    PKT_TUNE_BAD_L2    = 5,  /* the entry before it is neither Ether nor VLAN nor MPLS */
+    PKT_TUNE_BAD_HDR   = 6,  /* IPv4 byte 0 != 0x45 or total length < 20; IPv6 version != 6 */
+    PKT_TUNE_TRUNC     = 7,  /* the inner L3 length runs past the packet */
+    PKT_TUNE_TOO_BIG   = 8,  /* the outer length would pass 65535 */
+    PKT_TUNE_DEPTH     = 9   /* more than PKT_MAX_HDRS rows */
+} pkt_tune_status_t;
+#define PKT_TUNE_STATUS_COUNT 10
+typedef enum pkt_tund_status {
+    PKT_TUND_OK         = 0,  /* one output */
+    PKT_TUND_SKIPPED    = 1,
+    PKT_TUND_NO_IP      = 2,
+    PKT_TUND_SPAN       = 3,  /* the outer IP or tunnel header is not inside the packet */
+    PKT_TUND_BAD_HDR    = 4,  /* IPv4 byte 0 != 0x45, IPv6 version != 6, or a UDP length that disagrees with the IP length */
+    PKT_TUND_FRAGMENT   = 5,  /* any outer IPv4 fragment */
+    PKT_TUND_NOT_TUNNEL = 6,  /* the chain entries behind the IP entry are no tunnel's */
+    PKT_TUND_BAD_GRE    = 7,  /* checksum, sequence or routing, a version other than 0, an unknown protocol */
+    PKT_TUND_NO_MATCH   = 8,  /* no table entry */
+    PKT_TUND_TRUNC      = 9,  /* the outer length field runs past the packet */
+    PKT_TUND_NO_INNER   = 10  /* nothing (or too little) inside */
+} pkt_tund_status_t;
+#define PKT_TUND_STATUS_COUNT 11
+#define PKT_TUN_F_KEY         1u
+#define PKT_TUN_F_DF          2u
+#define PKT_TUN_F_INHERIT_TOS 4u
+#define PKT_TUN_F_UDP_CSUM    8u
+#define PKT_TUN_F_ANY_REMOTE  16u
+#define PKT_TUN_NO_WRITE      1u          /* call flags: decide and total everything, store no packet byte and no per-output array */
+#define PKT_TUN_NONE          0xFFFFFFFFu /* out_index[i] / src_index[q] / tunnel_out[i] when there is none */
+#define PKT_TUN_MAX_ENTRIES   65536u
+size_t pkt_sizeof_tunnel_entry(void);
+int pkt_tunnel_create(pkt_ctx_t *ctx, const pkt_tunnel_entry_t *entries, uint32_t count, pkt_tunnel_t **tun);
+int pkt_tunnel_create_host(const pkt_tunnel_entry_t *entries, uint32_t count, pkt_tunnel_t **tun);
+int pkt_tunnel_destroy(pkt_tunnel_t *tun);
+const char *pkt_tunnel_last_error(const pkt_tunnel_t *tun);
+int pkt_tunnel_encap_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                           uint32_t flags, const pkt_tunnel_t *tun, const uint32_t *tunnel, uint32_t tunnel_all,
+                           const uint32_t *entropy, uint32_t ident, const uint8_t *select,
+                           uint8_t *status, uint32_t *out_index,
+                           uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                           uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                           const pkt_chain_t *out_chain,
+                           uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out, void *stream);
+int pkt_tunnel_encap_batch_async(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                                 uint32_t flags, const pkt_tunnel_t *tun, const uint32_t *tunnel, uint32_t tunnel_all,
+                                 const uint32_t *entropy, uint32_t ident, const uint8_t *select,
+                                 uint8_t *status, uint32_t *out_index,
+                                 uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                                 uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                                 const pkt_chain_t *out_chain, uint64_t *hits, void *stream);
+int pkt_tunnel_encap_result(pkt_ctx_t *ctx, uint64_t *bytes_out_total, uint64_t *n_out);
+int pkt_tunnel_encap_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                          uint32_t flags, const pkt_tunnel_t *tun, const uint32_t *tunnel, uint32_t tunnel_all,
+                          const uint32_t *entropy, uint32_t ident, const uint8_t *select,
+                          uint8_t *status, uint32_t *out_index,
+                          uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                          uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                          const pkt_chain_t *out_chain,
+                          uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
+int pkt_tunnel_decap_batch(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                           uint32_t flags, const pkt_tunnel_t *tun, const uint8_t *select,
+                           uint8_t *status, uint32_t *out_index, uint32_t *tunnel_out,
+                           uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                           uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                           const pkt_chain_t *out_chain,
+                           uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out, void *stream);
+int pkt_tunnel_decap_batch_async(pkt_ctx_t *ctx, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                                 uint32_t flags, const pkt_tunnel_t *tun, const uint8_t *select,
+                                 uint8_t *status, uint32_t *out_index, uint32_t *tunnel_out,
+                                 uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                                 uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                                 const pkt_chain_t *out_chain, uint64_t *hits, void *stream);
+int pkt_tunnel_decap_result(pkt_ctx_t *ctx, uint64_t *bytes_out_total, uint64_t *n_out);
+int pkt_tunnel_decap_host(const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                          uint32_t flags, const pkt_tunnel_t *tun, const uint8_t *select,
+                          uint8_t *status, uint32_t *out_index, uint32_t *tunnel_out,
+                          uint8_t *dst, uint64_t dst_len, uint64_t out_cap,
+                          uint64_t *out_off, uint32_t *out_len, uint32_t *src_index,
+                          const pkt_chain_t *out_chain,
+                          uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
 
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);

@@ -24,7 +24,8 @@ int pkt_ctx_destroy(pkt_ctx_t* ctx) {
     // A ctx that never touched the device makes no HIP call (pkt_pcap_stream_close and error paths destroy
     // such ones).  hp.s[0]: the host pipeline's streams come before any of its buffers and events.
     const bool owns = ctx->tv_flag || ctx->tv_win || ctx->tv_win_ev || ctx->mx.dev || ctx->pc.buf || ctx->pc.ctl ||
-                      ctx->pw.buf || ctx->pw.ctl || ctx->fr.buf || ctx->fr.ctl || ctx->rs.buf || ctx->rs.ctl || ctx->ic.buf || ctx->ic.ctl || ctx->cmp.acc || ctx->cmp.ctl || hp.s[0];
+                      ctx->pw.buf || ctx->pw.ctl || ctx->fr.buf || ctx->fr.ctl || ctx->rs.buf || ctx->rs.ctl || ctx->ic.buf || ctx->ic.ctl || ctx->te.buf || ctx->te.ctl || ctx->td.buf ||
+                      ctx->td.ctl || ctx->cmp.acc || ctx->cmp.ctl || hp.s[0];
     if (owns) {
         (void)hipSetDevice(ctx->device);
         (void)hipDeviceSynchronize();  // nothing queued still uses what is freed below
@@ -37,7 +38,7 @@ int pkt_ctx_destroy(pkt_ctx_t* ctx) {
         (void)hipHostFree(ctx->mx.host);
         (void)hipFree(ctx->pc.buf);
         (void)hipHostFree(ctx->pc.ctl);
-        for (OutScratch* o : {static_cast<OutScratch*>(&ctx->pw), &ctx->fr, &ctx->rs, &ctx->ic}) o->release();
+        for (OutScratch* o : {static_cast<OutScratch*>(&ctx->pw), &ctx->fr, &ctx->rs, &ctx->ic, &ctx->te, &ctx->td}) o->release();
         (void)hipFree(ctx->cmp.acc);
         (void)hipHostFree(ctx->cmp.ctl);
         for (int k = 0; k < HostPipe::kSlots; k++) {

@@ -1,7 +1,7 @@
 // pktgpu_ctx.hpp — the pkt_ctx behind the C ABI's opaque handle and the internal entry points the sources
 // share: the kernel sources (pktgpu.hip: parse; pktgpu_rewrite.hip: getters, to_vec, setters; pktgpu_pcap.hip /
 // pktgpu_pcapw.hip: pcap indexer / writer; pktgpu_compare.hip, pktgpu_edit.hip, pktgpu_l4csum.hip, pktgpu_flow.hip, pktgpu_match.hip,
-// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_reasm.hip, pktgpu_icmp.hip, pktgpu_nat.hip and the
+// pktgpu_dispatch.hip, pktgpu_lpm.hip, pktgpu_fwd.hip, pktgpu_frag.hip, pktgpu_reasm.hip, pktgpu_icmp.hip, pktgpu_nat.hip, pktgpu_tunnel.hip and the
 // pktgpu_outbatch.hip they share, pktgpu_scan.hip, pktgpu_gen.hip, pktgpu_gather.hip) and the
 // host-only ones (pktgpu_ctx.cpp: lifecycle and knobs; pktgpu_hostpath.cpp: host-memory paths; pktgpu_mgpu.cpp).
 #pragma once
@@ -85,7 +85,7 @@ struct PcapScratch : QueuedResult {
 inline uint64_t round16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
 
 // Device scratch of an entry that packs outputs behind a device-side scan, grown on demand, with the entry's queued
-// result.  pkt_frag_batch, pkt_reasm_batch and pkt_icmp_err_batch (pktgpu_outbatch.hpp's contract) keep the totals'
+// result.  pkt_frag_batch, pkt_reasm_batch, pkt_icmp_err_batch and pkt_tunnel_encap / _decap_batch (pktgpu_outbatch.hpp's contract) keep the totals'
 // device words, the tile sums and their per-packet plans, records and tables in it; their result words are [total
 // rounded bytes, outputs, nonzero = they did not fit], pending: a call queued by the entry's _async form.
 struct OutScratch : QueuedResult {
@@ -161,6 +161,7 @@ struct pkt_ctx {
     PcapScratch pc;
     PcapWriteScratch pw;
     OutScratch fr, rs, ic;  // pkt_frag_batch, pkt_reasm_batch, pkt_icmp_err_batch: one call in flight each
+    OutScratch te, td;      // pkt_tunnel_encap_batch, pkt_tunnel_decap_batch
     CompareScratch cmp;
     MaxScratch mx;
     uint32_t window = 0;  // 0 = auto

@@ -17,6 +17,7 @@
 #include "pktgpu_reasm.hpp"
 #include "pktgpu_scan.hpp"
 #include "pktgpu_icmp.hpp"
+#include "pktgpu_tunnel.hpp"
 #include "pktgpu_nat.hpp"
 
 namespace {
@@ -1714,6 +1715,233 @@ int pkt_icmp_err_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t w
     }
     out_empty_tail(q, out_cap, out_off, out_len, src_index, static_cast<uint8_t*>(nullptr), oc.nh);
     return PKT_SUCCESS;
+}
+
+// ---- pkt_tunnel_*: the host handle, and encap / decap on host pointers (the CPU twins of pktgpu_tunnel.hip): two
+// sequential passes over the packets with the search, the decisions, the header words, the rows and the refusals of
+// pktgpu_tunnel.hpp, which the kernels share.  The first pass decides and totals; the second, when the outputs fit,
+// writes them a byte at a time and sums the inner bytes with the plain RFC 1071 loop.
+static thread_local std::string t_tun_create_err;  // pkt_tunnel_last_error(NULL): the thread's last failed create_host
+
+namespace {
+
+// the bytes [pos, pos + 4 * nw) of a packet of `len` bytes as little-endian dwords, zero past the packet
+void tun_read(const uint8_t* s, uint32_t len, uint32_t pos, uint32_t nw, uint32_t* o) {
+    for (uint32_t k = 0; k < nw; k++) o[k] = 0;
+    for (uint32_t k = 0; k < 4u * nw && pos + k < len; k++) o[k >> 2] |= (uint32_t)s[pos + k] << (8u * (k & 3u));
+}
+
+TunFind tun_search_host(const pkt_chain_t* chain, uint64_t n, uint64_t i, uint32_t which_ip, uint32_t& nh) {
+    nh = chain->n_hdrs[i];
+    nh = nh > PKT_MAX_HDRS ? PKT_MAX_HDRS : nh;
+    TunFind f;
+    for (uint32_t j = 0; j < nh; j++) tun_find_step(f, which_ip, j, chain->hdr_type[j * n + i], chain->hdr_off[j * n + i]);
+    return f;
+}
+
+TunPlan tun_encap_plan_host(const BatchSrc& src, const pkt_chain_t* chain, uint64_t n, uint64_t i, uint32_t which_ip,
+                            const TunView& v, const uint32_t* tunnel, uint32_t tunnel_all, const uint32_t* entropy,
+                            const uint8_t* select) {
+    TunPlan p{};
+    p.st = PKT_TUNE_SKIPPED;
+    if (select && !select[i]) return p;
+    const uint32_t t = tunnel ? tunnel[i] : tunnel_all;
+    p.st = PKT_TUNE_NO_TUNNEL;
+    if (t >= v.n) return p;
+    const uint64_t off = pkt_off(src, i);
+    const uint32_t len = pkt_len(src, i, off);
+    uint32_t nh, rd;
+    const TunFind f = tun_search_host(chain, n, i, which_ip, nh);
+    const TunEnt& e = v.ent[t];
+    p.st = tun_encap_find_status(f, e, len, rd);
+    if (p.st != PKT_TUNE_OK) return p;
+    uint32_t h[2] = {0, 0};
+    if (rd != kTunNoRead) tun_read(src.slab + off, len, rd, 2, h);
+    tun_encap_decide(p, f, e, t, nh, len, rd, h, entropy ? entropy[i] : 0u);
+    return p;
+}
+
+TunPlan tun_decap_plan_host(const BatchSrc& src, const pkt_chain_t* chain, uint64_t n, uint64_t i, uint32_t which_ip,
+                            const TunView& v, const uint8_t* select, uint32_t& tout) {
+    TunPlan p{};
+    tout = PKT_TUN_NONE;
+    p.st = PKT_TUND_SKIPPED;
+    if (select && !select[i]) return p;
+    const uint64_t off = pkt_off(src, i);
+    const uint32_t len = pkt_len(src, i, off);
+    uint32_t nh;
+    const TunFind f = tun_search_host(chain, n, i, which_ip, nh);
+    p.st = tun_decap_find_status(f, len);
+    if (p.st != PKT_TUND_OK) return p;
+    const uint32_t H = f.ipt == PKT_HDR_IPV4 ? 20u : 40u;
+    uint32_t ip[10], th[4];
+    tun_read(src.slab + off, len, f.ipo, 10, ip);
+    tun_read(src.slab + off, len, f.ipo + H, 4, th);
+    tun_decap_decide(p, f, nh, len, ip, th, v, tout);
+    return p;
+}
+
+// the second pass: output q of source packet i at dst + pos, by its plan
+void tun_write_host(const TunPlan& p, const TunEnt* e, const uint8_t* s, uint64_t q, uint32_t ident, uint8_t* d) {
+    const uint32_t ol = tun_out_len(p);
+    memcpy(d, s, p.P);
+    if (p.patch) {
+        d[p.P - 2u] = p.et6 ? 0x86u : 0x08u;
+        d[p.P - 1u] = p.et6 ? 0xDDu : 0x00u;
+    }
+    const uint8_t* inner = s + p.P + p.S;
+    memcpy(d + p.P + p.hl, inner, p.I);
+    if (p.hl) {
+        uint32_t w[18];
+        const uint32_t part = tun_headers(p, *e, q, ident, w);
+        for (uint32_t k = 0; k < p.hl; k++) d[p.P + k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
+        if (p.cs) {
+            uint32_t sum = 0;
+            for (uint32_t k = 0; k < p.I; k++) {
+                sum += k & 1u ? inner[k] : (uint32_t)inner[k] << 8;
+                sum = (sum & 0xFFFFu) + (sum >> 16);
+            }
+            const uint32_t c = tun_udp_csum(part, sum), at = 4u * tun_csum_word(*e);
+            d[at] = (uint8_t)(c >> 8);
+            d[at + 1u] = (uint8_t)c;
+        }
+    }
+    memset(d + ol, 0, out_round16(ol) - ol);
+}
+
+void tun_rows_host(const TunPlan& p, const TunEnt* e, const pkt_chain_t* chain, uint64_t n, uint64_t i, const OutChainCols& oc,
+                   uint64_t out_cap, uint64_t q) {
+    const uint32_t rows = tun_out_rows(p);
+    if (oc.nh) oc.nh[q] = (uint8_t)rows;
+    for (uint32_t r = 0; r < rows; r++) {
+        uint32_t ty = 0, of = 0, j = 0;
+        int32_t delta = 0;
+        if (!tun_out_row(p, e, r, ty, of, j, delta)) {
+            ty = chain->hdr_type[j * n + i];
+            of = (uint32_t)((int32_t)chain->hdr_off[j * n + i] + delta);
+        }
+        if (oc.ty) oc.ty[r * out_cap + q] = (uint8_t)ty;
+        if (oc.of) oc.of[r * out_cap + q] = (uint16_t)of;
+    }
+}
+
+// both twins: plan(i) gives packet i's plan (and sets tout)
+extern "C++" template <typename Plan>
+int tun_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t flags, const pkt_tunnel* tun, uint32_t ok, uint32_t ident,
+             uint8_t* status, uint32_t* out_index, uint32_t* tunnel_out, uint8_t* dst, uint64_t dst_len, uint64_t out_cap,
+             uint64_t* out_off, uint32_t* out_len, uint32_t* src_index, const pkt_chain_t* out_chain, uint64_t* hits,
+             uint64_t* bytes_out_total, uint64_t* n_out, const Plan& plan) {
+    const uint64_t n = b->n;
+    const BatchSrc src = batch_src(b);
+    uint64_t q = 0, bytes = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t tout = PKT_TUN_NONE;
+        const TunPlan p = plan(i, tout);
+        const bool sent = p.st == ok;
+        if (status) status[i] = (uint8_t)p.st;
+        if (out_index) out_index[i] = sent ? (uint32_t)q : PKT_TUN_NONE;
+        if (tunnel_out) tunnel_out[i] = tout;
+        if (hits) hits[p.st] += 1;
+        if (sent) {
+            q += 1;
+            bytes += out_round16(tun_out_len(p));
+        }
+    }
+    if (bytes_out_total) *bytes_out_total = bytes;
+    if (n_out) *n_out = q;
+    if (flags & PKT_TUN_NO_WRITE) return PKT_SUCCESS;
+    if (out_overflow(q, bytes, out_cap, dst_len)) return PKT_ERR_INVALID_ARG;
+    const OutChainCols oc = out_chain_cols(out_chain);
+    q = 0;
+    uint64_t pos = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t tout;
+        const TunPlan p = plan(i, tout);
+        if (p.st != ok) continue;
+        const TunEnt* e = p.hl ? &tun->v.ent[p.t] : nullptr;
+        tun_write_host(p, e, src.slab + pkt_off(src, i), q, ident, dst + pos);
+        out_off[q] = pos;
+        out_len[q] = tun_out_len(p);
+        if (src_index) src_index[q] = (uint32_t)i;
+        tun_rows_host(p, e, chain, n, i, oc, out_cap, q);
+        pos += out_round16(tun_out_len(p));
+        q++;
+    }
+    out_empty_tail(q, out_cap, out_off, out_len, src_index, static_cast<uint8_t*>(nullptr), oc.nh);
+    return PKT_SUCCESS;
+}
+
+}  // namespace
+
+size_t pkt_sizeof_tunnel_entry(void) { return sizeof(pkt_tunnel_entry_t); }
+
+int pkt_tunnel_create_host(const pkt_tunnel_entry_t* entries, uint32_t count, pkt_tunnel_t** out) {
+    if (!out) {
+        t_tun_create_err = "pkt_tunnel_create_host: null argument";
+        return PKT_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    pkt_tunnel* t = new pkt_tunnel;
+    const int rc = tun_compile(entries, count, t->img, t_tun_create_err);
+    if (rc != PKT_SUCCESS) {
+        delete t;
+        return rc;
+    }
+    t->v = TunView{t->img.ent.data(), t->img.slots.data(), count, (uint32_t)t->img.slots.size() - 1u};
+    *out = t;
+    return PKT_SUCCESS;
+}
+
+int pkt_tunnel_destroy(pkt_tunnel_t* t) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    const int rc = t->destroy ? t->destroy(t) : PKT_SUCCESS;
+    delete t;
+    return rc;
+}
+
+const char* pkt_tunnel_last_error(const pkt_tunnel_t* t) { return t ? t->err.c_str() : t_tun_create_err.c_str(); }
+
+int pkt_tunnel_encap_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
+                          const pkt_tunnel_t* tun, const uint32_t* tunnel, uint32_t tunnel_all, const uint32_t* entropy,
+                          uint32_t ident, const uint8_t* select, uint8_t* status, uint32_t* out_index, uint8_t* dst,
+                          uint64_t dst_len, uint64_t out_cap, uint64_t* out_off, uint32_t* out_len, uint32_t* src_index,
+                          const pkt_chain_t* out_chain, uint64_t* hits, uint64_t* bytes_out_total, uint64_t* n_out) {
+    if (bytes_out_total) *bytes_out_total = 0;
+    if (n_out) *n_out = 0;
+    if (tun) tun->err.clear();
+    if (const char* msg = tun_call_error(b, chain, which_ip, flags, tun, tunnel, entropy, dst, out_cap, out_off, out_len, hits,
+                                         false, 0)) {
+        (tun ? tun->err : t_tun_create_err) = std::string("pkt_tunnel_encap_host: ") + msg;
+        return PKT_ERR_INVALID_ARG;
+    }
+    const BatchSrc src = batch_src(b);
+    const auto plan = [&](uint64_t i, uint32_t& tout) {
+        tout = PKT_TUN_NONE;
+        return tun_encap_plan_host(src, chain, b->n, i, which_ip, tun->v, tunnel, tunnel_all, entropy, select);
+    };
+    return tun_host(b, chain, flags, tun, PKT_TUNE_OK, ident, status, out_index, nullptr, dst, dst_len, out_cap, out_off,
+                    out_len, src_index, out_chain, hits, bytes_out_total, n_out, plan);
+}
+
+int pkt_tunnel_decap_host(const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
+                          const pkt_tunnel_t* tun, const uint8_t* select, uint8_t* status, uint32_t* out_index,
+                          uint32_t* tunnel_out, uint8_t* dst, uint64_t dst_len, uint64_t out_cap, uint64_t* out_off,
+                          uint32_t* out_len, uint32_t* src_index, const pkt_chain_t* out_chain, uint64_t* hits,
+                          uint64_t* bytes_out_total, uint64_t* n_out) {
+    if (bytes_out_total) *bytes_out_total = 0;
+    if (n_out) *n_out = 0;
+    if (tun) tun->err.clear();
+    if (const char* msg = tun_call_error(b, chain, which_ip, flags, tun, tunnel_out, nullptr, dst, out_cap, out_off, out_len,
+                                         hits, false, 0)) {
+        (tun ? tun->err : t_tun_create_err) = std::string("pkt_tunnel_decap_host: ") + msg;
+        return PKT_ERR_INVALID_ARG;
+    }
+    const BatchSrc src = batch_src(b);
+    const auto plan = [&](uint64_t i, uint32_t& tout) {
+        return tun_decap_plan_host(src, chain, b->n, i, which_ip, tun->v, select, tout);
+    };
+    return tun_host(b, chain, flags, tun, PKT_TUND_OK, 0, status, out_index, tunnel_out, dst, dst_len, out_cap, out_off,
+                    out_len, src_index, out_chain, hits, bytes_out_total, n_out, plan);
 }
 
 // The PacketSlice of packet i from host chain columns (lib.rs:136-140: hdrs in `insert` order,

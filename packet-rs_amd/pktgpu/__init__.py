@@ -763,6 +763,12 @@ class Parser:
         schema.NAT_STATIC_DTYPE.  host=True gives the host handle (numpy arrays in and out, no device)."""
         return Nat(None if host else self, pool, ports, slots, static)
 
+    def tunnels(self, entries, host=False):
+        """pkt_tunnel_create: a table of 1..65536 VXLAN / GRE / IP-in-IP tunnels on this parser's device -> Tunnels,
+        whose encap and decap take a parsed batch.  `entries`: a numpy array of schema.TUNNEL_ENTRY_DTYPE, or dicts
+        as tunnel_entries takes them.  host=True gives the host handle (numpy arrays in and out, no device)."""
+        return Tunnels(None if host else self, entries)
+
     def fragment(self, batch, chain, mtu=1500, select=None, which_ip=0, only_split=False, plan_only=False,
                  out_cap=None, dst_bytes=None, hits=None, host=False, stream=None):
         """pkt_frag_batch: every packet whose L3 length is above its mtu becomes IPv4 fragments, every other packet
@@ -2207,6 +2213,163 @@ def _icmp_errors(parser, batch, chain, reason, fwd_status, frag_status, mtu, src
                                  None if cmap is None else cmap.ctypes.data, *per_packet(mtu, np.uint16))
     return _produce(parser, _ICMPE, batch, chain, select, which_ip, 0, inputs, plan_only, out_cap, dst_bytes, hits, host,
                     stream)
+
+
+(TUNE_OK, TUNE_SKIPPED, TUNE_NO_TUNNEL, TUNE_NO_IP, TUNE_SPAN, TUNE_BAD_L2, TUNE_BAD_HDR, TUNE_TRUNC, TUNE_TOO_BIG,
+ TUNE_DEPTH) = range(10)
+(TUND_OK, TUND_SKIPPED, TUND_NO_IP, TUND_SPAN, TUND_BAD_HDR, TUND_FRAGMENT, TUND_NOT_TUNNEL, TUND_BAD_GRE, TUND_NO_MATCH,
+ TUND_TRUNC, TUND_NO_INNER) = range(11)
+TUN_NONE, TUN_NO_WRITE = schema.TUN_NONE, schema.TUN_NO_WRITE
+
+
+class TunnelResult(_Produced):
+    """What Tunnels.encap and Tunnels.decap give.  Per source packet: status (uint8: pktgpu.TUNE_* / TUND_*), out_index
+    (uint32: the packet's output, TUN_NONE where there is none) and, for decap, tunnel_out (uint32: the matched entry,
+    TUN_NONE where none was).  The totals: n_out, bytes_out.  Unless plan_only, per output (arrays of out_cap entries,
+    empty past n_out): slab, offsets, lens, src_index and out_chain ({"n_hdrs", "hdr_type", "hdr_off"}, slot-major over
+    out_cap); batch() is the output as the batch dict the other calls take.  hits: the per-status counters, if asked for."""
+    tunnel_out = None
+
+
+_TUNE = dict(what="tunnels.encap", fn="pkt_tunnel_encap", result=TunnelResult, nc=schema.TUNE_STATUS_COUNT,
+             no_write=schema.TUN_NO_WRITE, per_packet=(("status", np.uint8), ("out_index", np.uint32)), extra=None)
+_TUND = dict(what="tunnels.decap", fn="pkt_tunnel_decap", result=TunnelResult, nc=schema.TUND_STATUS_COUNT,
+             no_write=schema.TUN_NO_WRITE,
+             per_packet=(("status", np.uint8), ("out_index", np.uint32), ("tunnel_out", np.uint32)), extra=None)
+
+
+def tunnel_entries(entries):
+    """Tunnel table entries -> a numpy array of schema.TUNNEL_ENTRY_DTYPE.  An entry is a dict: kind ("vxlan" / "gre" /
+    "ipip" or schema.TUN_*), src and dst (address strings, or 4 / 16 bytes; they give ipver), and optionally ttl, tos,
+    id (the VNI or the GRE key), sport (lo, hi), eth_dst / eth_src ("aa:bb:.." or 6 bytes), flags (schema.TUN_F_*)."""
+    import socket
+    if isinstance(entries, np.ndarray):
+        if entries.dtype != schema.TUNNEL_ENTRY_DTYPE:
+            raise ValueError("tunnels: an entries array has dtype schema.TUNNEL_ENTRY_DTYPE")
+        return np.ascontiguousarray(entries)
+
+    def addr(a):
+        if isinstance(a, str):
+            a = socket.inet_pton(socket.AF_INET6 if ":" in a else socket.AF_INET, a)
+        a = bytes(a)
+        if len(a) not in (4, 16):
+            raise ValueError("tunnels: an address is a string or 4 / 16 bytes")
+        return a
+
+    def mac(m):
+        m = bytes.fromhex(m.replace(":", "")) if isinstance(m, str) else bytes(m)
+        if len(m) != 6:
+            raise ValueError("tunnels: a MAC address is 6 bytes")
+        return m
+
+    out = np.zeros(len(entries), schema.TUNNEL_ENTRY_DTYPE)
+    for k, e in enumerate(entries):
+        src, dst = addr(e["src"]), addr(e["dst"])
+        if len(src) != len(dst):
+            raise ValueError("tunnels: src and dst of an entry are of one IP version")
+        r = out[k]
+        kind = e["kind"]
+        r["kind"] = schema.TUN_KIND[kind] if isinstance(kind, str) else int(kind)
+        r["ipver"] = 4 if len(src) == 4 else 6
+        r["ttl"], r["tos"], r["flags"], r["id"] = e.get("ttl", 0), e.get("tos", 0), e.get("flags", 0), e.get("id", 0)
+        r["sport_lo"], r["sport_hi"] = e.get("sport", (49152, 65535))
+        r["src"][:len(src)] = np.frombuffer(src, np.uint8)
+        r["dst"][:len(dst)] = np.frombuffer(dst, np.uint8)
+        r["eth_dst"][:] = np.frombuffer(mac(e.get("eth_dst", bytes(6))), np.uint8)
+        r["eth_src"][:] = np.frombuffer(mac(e.get("eth_src", bytes(6))), np.uint8)
+    return out
+
+
+class Tunnels:
+    """A tunnel table (pkt_tunnel_create): VXLAN, GRE and IP-in-IP entries that `encap` puts packets into and `decap`
+    takes them out of; Parser.tunnels makes one, Tunnels(None, entries) is the host form (pkt_tunnel_create_host: numpy
+    arrays in and out, no device).  The table is read-only: calls on several streams share it.
+
+        tun = p.tunnels([dict(kind="vxlan", src="192.0.2.1", dst="192.0.2.2", id=2000, flags=schema.TUN_F_UDP_CSUM)])
+        keys = p.flow_keys(batch, chain)
+        e = tun.encap(batch, chain, tunnel=0, entropy=keys)      # one VXLAN packet per packet, lengths and checksums set
+        fwd.run(e.batch(), e.out_chain, lpm=lpm, which_ip=0)     # route on the outer header
+        d = tun.decap(e.batch(), e.out_chain)                    # and back: d.batch() holds the inner frames
+    """
+
+    def __init__(self, parser, entries):
+        from . import _lib
+        self._lib = _lib
+        self._L = _lib.load()
+        self.parser = parser
+        self.entries = tunnel_entries(entries)
+        n = len(self.entries)
+        h = ctypes.c_void_p()
+        self._t = None
+        ptr = self.entries.ctypes.data if n else None
+        if parser is None:
+            rc = self._L.pkt_tunnel_create_host(ptr, n, ctypes.byref(h))
+            if rc != 0:
+                msg = self._L.pkt_tunnel_last_error(None)
+                raise ValueError(f"pkt_tunnel_create_host failed ({rc}): {msg.decode() if msg else ''}")
+        else:
+            parser._check(self._L.pkt_tunnel_create(parser._ctx, ptr, n, ctypes.byref(h)), "pkt_tunnel_create")
+        self._t = h
+
+    def __len__(self):
+        return len(self.entries)
+
+    def _run(self, e, batch, chain, inputs, select, which_ip, plan_only, out_cap, dst_bytes, hits, stream):
+        host = self.parser is None
+        try:
+            return _produce(self.parser, e, batch, chain, select, which_ip, 0, inputs, plan_only, out_cap, dst_bytes, hits,
+                            host, stream)
+        except ValueError as ex:  # the host twins keep their refusal's text in the handle
+            msg = self._L.pkt_tunnel_last_error(self._t) if host else None
+            if msg:
+                raise ValueError(f"{ex}: {msg.decode()}") from None
+            raise
+
+    def _entropy(self, entropy):
+        """None, a uint32 [n] array, or Parser.flow_keys' result: its "rss", else the low 32 bits of its "hash"."""
+        if not isinstance(entropy, dict):
+            return entropy
+        if entropy.get("rss") is not None:
+            return entropy["rss"]
+        h = entropy["hash"]
+        if isinstance(h, np.ndarray):
+            return (h & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        return h.view(_torch().uint32)[::2].contiguous()
+
+    def encap(self, batch, chain, tunnel=0, entropy=None, ident=0, select=None, which_ip=0, plan_only=False, out_cap=None,
+              dst_bytes=None, hits=None, stream=None):
+        """pkt_tunnel_encap_batch: every packet of the batch that may goes into its tunnel, all packed at
+        16-byte-aligned offsets of a new slab -> TunnelResult.  `tunnel`: one entry index for the batch, or a uint32 [n]
+        array (Lpm.lookup's nexthop, Forwarder.run's adj_index or port).  `entropy`: a uint32 [n] array or
+        Parser.flow_keys' result, which spreads VXLAN's UDP source port over the entry's range; None takes sport_lo.
+        `ident`: the outer IPv4 identification of output q is (ident + q) & 0xFFFF.  `which_ip`: the IP entry GRE and
+        IPIP wrap.  `select`, plan_only, out_cap / dst_bytes and hits (uint64 [10]) are as Parser.fragment takes them.
+        Parser.fragment over the result splits the OUTER datagram, so encap comes before it."""
+        entropy = self._entropy(entropy)
+        inputs = lambda per_packet: (self._t, *per_packet(tunnel, np.uint32),  # noqa: E731
+                                     None if entropy is None else per_packet(entropy, np.uint32)[0],
+                                     int(ident) & 0xFFFFFFFF)
+        return self._run(_TUNE, batch, chain, inputs, select, which_ip, plan_only, out_cap, dst_bytes, hits, stream)
+
+    def decap(self, batch, chain, select=None, which_ip=0, plan_only=False, out_cap=None, dst_bytes=None, hits=None,
+              stream=None):
+        """pkt_tunnel_decap_batch, the inverse of encap: every packet whose `which_ip`-th IP entry is the outer header of
+        a tunnel of the table gives its inner packet (VXLAN: the inner frame; GRE / IPIP: the L2 prefix and the inner IP
+        packet) -> TunnelResult with tunnel_out, the matched entry per packet.  Checksums are not verified
+        (Parser.l4_checksum first), outer IPv4 fragments are refused (Parser.reassemble first).  hits: uint64 [11]."""
+        inputs = lambda per_packet: (self._t,)  # noqa: E731
+        return self._run(_TUND, batch, chain, inputs, select, which_ip, plan_only, out_cap, dst_bytes, hits, stream)
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self._L.pkt_tunnel_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 (REASM_WHOLE, REASM_JOINED, REASM_PENDING, REASM_SKIPPED, REASM_NO_IP, REASM_SPAN, REASM_BAD_HDR, REASM_TRUNC,

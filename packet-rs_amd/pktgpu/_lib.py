@@ -114,6 +114,13 @@ class PktNatRecord(ctypes.Structure):
                 ("zero", ctypes.c_uint16), ("last_seen", ctypes.c_uint32)]
 
 
+class PktTunnelEntry(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint8), ("ipver", ctypes.c_uint8), ("ttl", ctypes.c_uint8), ("tos", ctypes.c_uint8),
+                ("flags", ctypes.c_uint32), ("id", ctypes.c_uint32), ("sport_lo", ctypes.c_uint16),
+                ("sport_hi", ctypes.c_uint16), ("src", ctypes.c_uint8 * 16), ("dst", ctypes.c_uint8 * 16),
+                ("eth_dst", ctypes.c_uint8 * 6), ("eth_src", ctypes.c_uint8 * 6), ("zero", ctypes.c_uint32)]
+
+
 class PktFwdAdj(ctypes.Structure):
     _fields_ = [("dmac", ctypes.c_uint8 * 6), ("smac", ctypes.c_uint8 * 6), ("port", ctypes.c_uint32),
                 ("mtu", ctypes.c_uint16), ("action", ctypes.c_uint8), ("zero", ctypes.c_uint8)]
@@ -337,6 +344,34 @@ SIGNATURES = {
     "pkt_nat_clear": (ctypes.c_int, [_P, _P]),
     "pkt_nat_destroy": (ctypes.c_int, [_P]),
     "pkt_nat_last_error": (ctypes.c_char_p, [_P]),
+    "pkt_sizeof_tunnel_entry": (ctypes.c_size_t, []),
+    "pkt_tunnel_create": (ctypes.c_int, [_P, _P, ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "pkt_tunnel_create_host": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "pkt_tunnel_destroy": (ctypes.c_int, [_P]),
+    "pkt_tunnel_last_error": (ctypes.c_char_p, [_P]),
+    "pkt_tunnel_encap_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                              ctypes.c_uint32, _P, _P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, ctypes.POINTER(PktChain), _P,
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _P]),
+    "pkt_tunnel_encap_batch_async": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain),
+                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P, ctypes.c_uint32, _P, ctypes.c_uint32,
+                                                    _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
+                                                    ctypes.POINTER(PktChain), _P, _P]),
+    "pkt_tunnel_encap_result": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_tunnel_encap_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                             ctypes.c_uint32, _P, _P, ctypes.c_uint32, _P, ctypes.c_uint32, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, ctypes.POINTER(PktChain), _P,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_tunnel_decap_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                              ctypes.c_uint32, _P, _P, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P,
+                                              _P, ctypes.POINTER(PktChain), _P, ctypes.POINTER(ctypes.c_uint64),
+                                              ctypes.POINTER(ctypes.c_uint64), _P]),
+    "pkt_tunnel_decap_batch_async": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain),
+                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, ctypes.c_uint64,
+                                                    ctypes.c_uint64, _P, _P, _P, ctypes.POINTER(PktChain), _P, _P]),
+    "pkt_tunnel_decap_result": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pkt_tunnel_decap_host": (ctypes.c_int, [ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                             ctypes.c_uint32, _P, _P, _P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P,
+                                             _P, ctypes.POINTER(PktChain), _P, ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.POINTER(ctypes.c_uint64)]),
     "pkt_ipv4_checksum_host": (ctypes.c_uint16, [ctypes.c_char_p, ctypes.c_size_t]),
     # packed outputs + multi-GPU (pkt_mgpu_*)
     "pkt_out_packed": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.POINTER(PktOut),
@@ -423,7 +458,8 @@ def load():
             or L.pkt_sizeof_scan_pattern() != ctypes.sizeof(PktScanPattern) \
             or L.pkt_sizeof_fwd_adj() != ctypes.sizeof(PktFwdAdj) \
             or L.pkt_sizeof_nat_static() != ctypes.sizeof(PktNatStatic) \
-            or L.pkt_sizeof_nat_record() != ctypes.sizeof(PktNatRecord):
+            or L.pkt_sizeof_nat_record() != ctypes.sizeof(PktNatRecord) \
+            or L.pkt_sizeof_tunnel_entry() != ctypes.sizeof(PktTunnelEntry):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L
     return L

@@ -131,6 +131,28 @@ def _icmp_map(pairs):
 ICMP_MAP_FWD = _icmp_map({FWD_TTL: ICMP_R_TIME_EXCEEDED, FWD_MTU: ICMP_R_TOO_BIG, FWD_NO_ADJ: ICMP_R_NET_UNREACH})
 ICMP_MAP_FRAG = _icmp_map({FRAG_DF: ICMP_R_TOO_BIG, FRAG_IPV6: ICMP_R_TOO_BIG})
 
+# pkt_tunnel_* (VXLAN / GRE / IP-in-IP encap and decap): kinds, entry flags, the statuses of the two calls
+TUN_VXLAN, TUN_GRE, TUN_IPIP = range(3)
+TUN_KIND = {"vxlan": TUN_VXLAN, "gre": TUN_GRE, "ipip": TUN_IPIP}
+TUN_F_KEY, TUN_F_DF, TUN_F_INHERIT_TOS, TUN_F_UDP_CSUM, TUN_F_ANY_REMOTE = 1, 2, 4, 8, 16
+(TUNE_OK, TUNE_SKIPPED, TUNE_NO_TUNNEL, TUNE_NO_IP, TUNE_SPAN, TUNE_BAD_L2, TUNE_BAD_HDR, TUNE_TRUNC, TUNE_TOO_BIG,
+ TUNE_DEPTH) = range(10)
+TUNE_STATUS = ["OK", "SKIPPED", "NO_TUNNEL", "NO_IP", "SPAN", "BAD_L2", "BAD_HDR", "TRUNC", "TOO_BIG", "DEPTH"]
+TUNE_STATUS_COUNT = 10
+(TUND_OK, TUND_SKIPPED, TUND_NO_IP, TUND_SPAN, TUND_BAD_HDR, TUND_FRAGMENT, TUND_NOT_TUNNEL, TUND_BAD_GRE, TUND_NO_MATCH,
+ TUND_TRUNC, TUND_NO_INNER) = range(11)
+TUND_STATUS = ["OK", "SKIPPED", "NO_IP", "SPAN", "BAD_HDR", "FRAGMENT", "NOT_TUNNEL", "BAD_GRE", "NO_MATCH", "TRUNC",
+               "NO_INNER"]
+TUND_STATUS_COUNT = 11
+TUN_NO_WRITE = 1         # call flags: decide and total everything, store no packet byte and no per-output array
+TUN_NONE = 0xFFFFFFFF    # out_index[i] / src_index[q] / tunnel_out[i] when there is none
+TUN_MAX_ENTRIES = 65536
+# pkt_tunnel_entry_t as a numpy record (addresses: wire bytes, IPv4 in the first 4)
+TUNNEL_ENTRY_DTYPE = np.dtype([("kind", np.uint8), ("ipver", np.uint8), ("ttl", np.uint8), ("tos", np.uint8),
+                               ("flags", np.uint32), ("id", np.uint32), ("sport_lo", np.uint16), ("sport_hi", np.uint16),
+                               ("src", np.uint8, 16), ("dst", np.uint8, 16), ("eth_dst", np.uint8, 6),
+                               ("eth_src", np.uint8, 6), ("zero", np.uint32)])
+
 # pkt_flow_key_t / pkt_flow_record_t as numpy records
 FLOW_KEY_DTYPE = np.dtype([("src", np.uint8, 16), ("dst", np.uint8, 16), ("sport", np.uint16), ("dport", np.uint16),
                            ("proto", np.uint8), ("ipver", np.uint8), ("zero", np.uint16)])
