@@ -403,6 +403,28 @@ class Parser {
               ctx_, "pkt_nat_batch");
     }
 
+    // A table of srTCM / trTCM policers on this context's device (pkt_meter_create); `adjust` is added to every
+    // packet's length.  The caller destroys it with pkt_meter_destroy after the calls queued on it; pkt_meter_reset /
+    // _export take the handle as it is.
+    pkt_meter_t* meters(const std::vector<pkt_meter_cfg_t>& cfg, int32_t adjust = 0) {
+        pkt_meter_t* t = nullptr;
+        check(pkt_meter_create(ctx_, cfg.data(), (uint32_t)cfg.size(), adjust, &t), ctx_, "pkt_meter_create");
+        return t;
+    }
+
+    // The metering of a batch (pkt_meter_batch): packet i is coloured against meter[i] (meter_all when `meter` is
+    // NULL; an index at or above the table's size leaves it unmetered) at time_ns[i] (now_ns when NULL).  With
+    // PKT_METER_MARK in `flags` the REMARK actions write the DSCP in place and `chain` is needed.  color / pass /
+    // marked / hits / bytes may each be NULL.  Asynchronous on `s`; one call at a time per handle.
+    void meter(pkt_meter_t* t, const pkt_batch_t& b, const uint32_t* meter, uint32_t meter_all, uint64_t now_ns,
+               const uint64_t* time_ns = nullptr, uint8_t* color = nullptr, uint8_t* pass = nullptr,
+               uint8_t* marked = nullptr, const uint8_t* in_color = nullptr, const uint8_t* select = nullptr,
+               const pkt_chain_t* chain = nullptr, uint32_t which_ip = 0, uint32_t flags = 0, uint64_t* hits = nullptr,
+               uint64_t* bytes = nullptr, hipStream_t s = nullptr) {
+        check(pkt_meter_batch(t, &b, chain, which_ip, flags, meter_all, meter, now_ns, time_ns, in_color, select, color, pass,
+                              marked, hits, bytes, s), ctx_, "pkt_meter_batch");
+    }
+
     // What Parser::fragment reports: the outputs and their rounded bytes (the capacities to retry with when `fits`
     // is false: the outputs did not fit out_cap / dst_len, and dst and the per-output arrays are unspecified).
     struct FragTotals {

@@ -2062,6 +2062,106 @@ int pkt_tunnel_decap_host(const pkt_batch_t *batch, const pkt_chain_t *chain, ui
                           const pkt_chain_t *out_chain,
                           uint64_t *hits, uint64_t *bytes_out_total, uint64_t *n_out);
 
+/* ---- pkt_meter_*: srTCM (RFC 2697) and trTCM (RFC 2698) token-bucket policers over a batch ----
+ * The reference defines nothing here; this section fixes the semantics.  A meter table handle owns the state of
+ * nmeters (1..PKT_METER_MAX_METERS) meters; one call takes a batch, colours every packet green, yellow or red against
+ * the meter its index names (a flow_id of pkt_flow_table_update, a rule id of pkt_match_batch, a port of
+ * pkt_fwd_batch), and passes, drops or remarks it.  The ABI stays v5 (additions only).
+ *
+ * pkt_meter_create: blocking, and the only allocating call.  cfg: HOST array of nmeters pkt_meter_cfg_t (32 bytes, every
+ * byte a checked field: the struct has no padding).  cir / pir: bytes per second, at most PKT_METER_MAX_RATE (2^40); pir
+ * is ignored by srTCM.  cbs / xbs: bytes, at most PKT_METER_MAX_BURST (2^26); xbs is EBS for srTCM and PBS for trTCM.
+ * mode: PKT_METER_SRTCM or PKT_METER_TRTCM.  flags: PKT_METER_F_COLOR_AWARE.  action[c] for colour c = green, yellow,
+ * red: PKT_METER_PASS / _DROP / _REMARK; dscp[c] (0..63) is what REMARK writes.  adjust is added to every packet's
+ * length (+20: preamble and gap; -14: L3 bytes); the sum is clamped at 0.  Anything out of range is
+ * PKT_ERR_INVALID_ARG with a text starting "pkt_meter" (pkt_ctx_last_error for pkt_meter_create,
+ * pkt_meter_last_error(NULL) on the calling thread for pkt_meter_create_host).  pkt_meter_create_host gives the same
+ * handle on host memory: every later call then takes HOST pointers and runs the sequential model itself.
+ *
+ * State per meter (pkt_meter_state_t, 72 bytes): the buckets c and x in units of 10^-9 byte, `last` in ns, and six
+ * exact counters: packets and bytes (the packet's length, without adjust) per colour.  Create and pkt_meter_reset
+ * (asynchronous on `stream`) set the buckets full (cbs * 10^9, xbs * 10^9), last = 0 and the counters to 0.
+ * pkt_meter_export (blocking): the state of meters [first, first + count) into `out`, device memory for a device handle.
+ *
+ * pkt_meter_batch: asynchronous on `stream`, one call at a time per handle, no host readback, no allocation.  meter:
+ * uint32_t[n] or NULL (every packet takes meter_all).  time_ns: uint64_t[n] or NULL (every packet takes now_ns).
+ * in_color, select: uint8_t[n] or NULL.  The model is sequential and in unbounded integers: the packets in index
+ * order, for packet i:
+ *  1. select != NULL && select[i] == 0, or k = (meter ? meter[i] : meter_all) >= nmeters (a flow_id of 0xFFFFFFFF falls
+ *     out here): color[i] = PKT_METER_UNMETERED (3), pass[i] = 1, marked[i] = 0, and nothing else happens.
+ *  2. t = time_ns ? time_ns[i] : now_ns.  B = max(0, len_i + adjust) * 10^9, len_i the packet's length under the
+ *     pkt_batch_t clamp rules.
+ *  3. Refill, only if t > last_k: dt = t - last_k, last_k = t (a time that runs backwards refills nothing and leaves
+ *     last).  srTCM: a = cir * dt, c' = min(cbs * 10^9, c + a), x' = min(xbs * 10^9, x + (c + a - c')).
+ *     trTCM: c' = min(cbs * 10^9, c + cir * dt), x' = min(xbs * 10^9, x + pir * dt).
+ *  4. ic = in_color[i] if in_color != NULL and the meter has PKT_METER_F_COLOR_AWARE, else green; above 2 counts as red.
+ *     srTCM: ic == green && c >= B: green, c -= B; else ic <= yellow && x >= B: yellow, x -= B; else red.
+ *     trTCM: ic == red || x < B: red; else ic == yellow || c < B: yellow, x -= B; else green, c -= B and x -= B.
+ *  5. color[i]; pass[i] = action[color] != PKT_METER_DROP.  The meter's counters and the call's hits[4] / bytes[4]
+ *     (index 3: the unmetered packets) take the packet; bytes counts len_i.  hits / bytes are ADDED to, as
+ *     pkt_fwd_batch's are: exactly n per call.
+ *  6. With the call flag PKT_METER_MARK and action[color] == PKT_METER_REMARK: the IP entry is found as in pkt_fwd_batch
+ *     step 2 (which_ip); if its 20 / 40 bytes lie inside the packet, the DSCP is written and marked[i] = 1.  IPv4:
+ *     byte 1's upper six bits, bytes 10..11 updated by RFC 1624 eq. 3 over that one word (a wrong checksum stays wrong
+ *     by as much).  IPv6: the six bits straddling bytes 0..1.  The ECN bits and everything else are kept; the stores
+ *     are byte stores.  Otherwise marked[i] = 0.  The colour and `pass` never depend on headers.  Forged chain columns
+ *     give unspecified packet bytes, never an access outside the packet.
+ * So a batch split at any index into two calls gives what the one call gives, meters are independent of each other,
+ * and the results are the same from run to run.  Every output may be NULL.
+ * PKT_ERR_INVALID_ARG before any launch (the text, starting "pkt_meter", in pkt_meter_last_error and, for a device
+ * handle, pkt_ctx_last_error): the batch and slab rules of pkt_fwd_batch, n >= 2^32, unknown flag bits, PKT_METER_MARK
+ * with a NULL chain (or a NULL chain column) or a which_ip in 16..0xFE, hits / bytes / time_ns not 8-byte aligned,
+ * meter not 4-byte aligned.  Without PKT_METER_MARK chain may be NULL and which_ip is not looked at.  n == 0 succeeds
+ * and launches nothing.  pkt_meter_destroy is the caller's to order after the queued calls.
+ * The worst case is one meter's long run: its packets are walked in order, 64 at a step, by one wave.
+ * Out of scope: RFC 4115; the DSCP-to-colour mapping of the incoming packet (a pkt_match_batch program's action gives
+ * in_color); hierarchical policers; shapers and queues; reconfiguring a live table; packet-rate (pps) meters. */
+typedef struct pkt_meter pkt_meter_t;
+typedef struct pkt_meter_cfg {     /* 32 bytes */
+    uint64_t cir;                  /* bytes per second */
+    uint64_t pir;
+    uint32_t cbs;                  /* bytes */
+    uint32_t xbs;
+    uint8_t  mode;                 /* PKT_METER_SRTCM / PKT_METER_TRTCM */
+    uint8_t  flags;                /* PKT_METER_F_COLOR_AWARE */
+    uint8_t  action[3];            /* for green, yellow, red */
+    uint8_t  dscp[3];              /* for green, yellow, red: what PKT_METER_REMARK writes */
+} pkt_meter_cfg_t;
+typedef struct pkt_meter_state {   /* 72 bytes */
+    uint64_t c;                    /* 10^-9 byte */
+    uint64_t x;
+    uint64_t last;                 /* ns */
+    uint64_t packets[3];           /* per colour */
+    uint64_t bytes[3];
+} pkt_meter_state_t;
+#define PKT_METER_GREEN     0u
+#define PKT_METER_YELLOW    1u
+#define PKT_METER_RED       2u
+#define PKT_METER_UNMETERED 3u
+#define PKT_METER_COLORS    4
+#define PKT_METER_SRTCM     0u
+#define PKT_METER_TRTCM     1u
+#define PKT_METER_F_COLOR_AWARE 1u
+#define PKT_METER_PASS      0u
+#define PKT_METER_DROP      1u
+#define PKT_METER_REMARK    2u
+#define PKT_METER_MARK      1u            /* call flags: do the REMARK stores */
+#define PKT_METER_MAX_METERS (1u << 24)
+#define PKT_METER_MAX_RATE   (1ull << 40)
+#define PKT_METER_MAX_BURST  (1u << 26)
+size_t pkt_sizeof_meter_cfg(void);
+size_t pkt_sizeof_meter_state(void);
+int pkt_meter_create(pkt_ctx_t *ctx, const pkt_meter_cfg_t *cfg, uint32_t nmeters, int32_t adjust, pkt_meter_t **m);
+int pkt_meter_create_host(const pkt_meter_cfg_t *cfg, uint32_t nmeters, int32_t adjust, pkt_meter_t **m);
+int pkt_meter_batch(pkt_meter_t *m, const pkt_batch_t *batch, const pkt_chain_t *chain, uint32_t which_ip,
+                    uint32_t flags, uint32_t meter_all, const uint32_t *meter, uint64_t now_ns, const uint64_t *time_ns,
+                    const uint8_t *in_color, const uint8_t *select, uint8_t *color, uint8_t *pass, uint8_t *marked,
+                    uint64_t *hits, uint64_t *bytes, void *stream);
+int pkt_meter_reset(pkt_meter_t *m, void *stream);
+int pkt_meter_export(pkt_meter_t *m, uint32_t first, uint32_t count, pkt_meter_state_t *out);
+int pkt_meter_destroy(pkt_meter_t *m);
+const char *pkt_meter_last_error(const pkt_meter_t *m);
+
 /* Packet::ipv4_checksum on the host (same arithmetic as the device kernel). */
 uint16_t pkt_ipv4_checksum_host(const uint8_t *hdr, size_t len);
 

@@ -19,6 +19,7 @@
 #include "pktgpu_icmp.hpp"
 #include "pktgpu_tunnel.hpp"
 #include "pktgpu_nat.hpp"
+#include "pktgpu_meter.hpp"
 
 namespace {
 
@@ -1339,6 +1340,99 @@ int pkt_nat_destroy(pkt_nat_t* t) {
 }
 
 const char* pkt_nat_last_error(const pkt_nat_t* t) { return t ? t->err.c_str() : t_nat_create_err.c_str(); }
+
+// ---- pkt_meter_*: the public calls, and the host handle, which is the sequential model of include/pktgpu.h itself (the
+// device handle: pktgpu_meter.hip).  The refill, the decision and the stores are pktgpu_meter.hpp's, which the kernels
+// share.
+size_t pkt_sizeof_meter_cfg(void) { return sizeof(pkt_meter_cfg_t); }
+size_t pkt_sizeof_meter_state(void) { return sizeof(pkt_meter_state_t); }
+
+static thread_local std::string t_meter_create_err;  // pkt_meter_last_error(NULL): the thread's last failed create_host
+
+namespace {
+
+int meter_host_batch(pkt_meter* t, const MeterCall& c) {
+    const MeterView& v = t->v;
+    for (uint64_t i = 0; i < c.n; i++) {
+        const uint64_t off = pkt_off(c.src, i);
+        const uint32_t len = pkt_len(c.src, i, off);
+        const uint32_t k = meter_of(c, v.nmeters, i);
+        uint32_t col = PKT_METER_UNMETERED, w = 0;
+        if (k != ~0u) {
+            w = v.word[k];
+            MeterRun run = meter_run_load(v.st[k]);
+            col = meter_run_packet(run, v.cfg[k], w, c.time ? c.time[i] : c.now, meter_cost(len, v.adjust),
+                                   meter_in_color(c, w, i), len);
+            meter_run_store(v.st[k], run);
+        }
+        meter_emit(c, i, col, w, off, len);
+        if (c.hits) c.hits[col] += 1;
+        if (c.bytes) c.bytes[col] += len;
+    }
+    return PKT_SUCCESS;
+}
+
+}  // namespace
+
+int pkt_meter_create_host(const pkt_meter_cfg_t* cfg, uint32_t nmeters, int32_t adjust, pkt_meter_t** out) {
+    if (!out) {
+        t_meter_create_err = "pkt_meter_create_host: null argument";
+        return PKT_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    if (const char* msg = meter_create_error(cfg, nmeters)) {
+        t_meter_create_err = std::string("pkt_meter_create_host: ") + msg;
+        return PKT_ERR_INVALID_ARG;
+    }
+    pkt_meter* t = new pkt_meter;
+    meter_pack(cfg, nmeters, t->h_cfg, t->h_word);
+    t->h_st.resize(nmeters);
+    t->v = MeterView{t->h_cfg.data(), t->h_word.data(), t->h_st.data(), nmeters, adjust};
+    for (uint32_t k = 0; k < nmeters; k++) meter_state_reset(t->h_st[k], t->h_cfg[k]);
+    *out = t;
+    return PKT_SUCCESS;
+}
+
+int pkt_meter_batch(pkt_meter_t* t, const pkt_batch_t* b, const pkt_chain_t* chain, uint32_t which_ip, uint32_t flags,
+                    uint32_t meter_all, const uint32_t* meter, uint64_t now_ns, const uint64_t* time_ns,
+                    const uint8_t* in_color, const uint8_t* select, uint8_t* color, uint8_t* pass, uint8_t* marked,
+                    uint64_t* hits, uint64_t* bytes, void* stream) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (const char* msg = meter_call_error(b, chain, which_ip, flags, meter, time_ns, hits, bytes))
+        return meter_fail(t, "pkt_meter_batch", msg);
+    if (b->n == 0) return PKT_SUCCESS;
+    if (const char* msg = meter_batch_error(b, chain, flags, t->ops != nullptr)) return meter_fail(t, "pkt_meter_batch", msg);
+    const bool mark = flags & PKT_METER_MARK;
+    const MeterCall c{batch_src(b), b->n, mark ? chain->n_hdrs : nullptr, mark ? chain->hdr_type : nullptr,
+                      mark ? chain->hdr_off : nullptr, which_ip, flags, meter_all, meter, now_ns, time_ns, in_color, select,
+                      color, pass, marked, hits, bytes};
+    return t->ops ? t->ops->batch(t, c, stream) : meter_host_batch(t, c);
+}
+
+int pkt_meter_reset(pkt_meter_t* t, void* stream) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (t->ops) return t->ops->reset(t, stream);
+    for (uint32_t k = 0; k < t->v.nmeters; k++) meter_state_reset(t->h_st[k], t->h_cfg[k]);
+    return PKT_SUCCESS;
+}
+
+int pkt_meter_export(pkt_meter_t* t, uint32_t first, uint32_t count, pkt_meter_state_t* out) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    if (first > t->v.nmeters || count > t->v.nmeters - first) return meter_fail(t, "pkt_meter_export", "first + count above nmeters");
+    if (count && !out) return meter_fail(t, "pkt_meter_export", "null out");
+    if (t->ops) return t->ops->xport(t, first, count, out);
+    if (count) memcpy(out, t->h_st.data() + first, (size_t)count * sizeof(pkt_meter_state_t));
+    return PKT_SUCCESS;
+}
+
+int pkt_meter_destroy(pkt_meter_t* t) {
+    if (!t) return PKT_ERR_INVALID_ARG;
+    const int rc = t->ops ? t->ops->destroy(t) : PKT_SUCCESS;
+    delete t;
+    return rc;
+}
+
+const char* pkt_meter_last_error(const pkt_meter_t* t) { return t ? t->err.c_str() : t_meter_create_err.c_str(); }
 
 // ---- pkt_frag_batch on host pointers (the CPU twin of pktgpu_frag.hip): two sequential passes over the packets with
 // the decision, the fragment header and the refusals of pktgpu_frag.hpp, which the kernels share.  The first pass

@@ -769,6 +769,13 @@ class Parser:
         as tunnel_entries takes them.  host=True gives the host handle (numpy arrays in and out, no device)."""
         return Tunnels(None if host else self, entries)
 
+    def meters(self, cfgs, adjust=0, host=False):
+        """pkt_meter_create: a table of 1..2^24 srTCM / trTCM token-bucket policers on this parser's device -> Meters.
+        `cfgs`: a numpy array of schema.METER_CFG_DTYPE, or dicts as meter_cfgs takes them.  `adjust` is added to
+        every packet's length (+20: preamble and gap, -14: L3 bytes).  host=True gives the host handle (numpy arrays
+        in and out, no device)."""
+        return Meters(None if host else self, cfgs, adjust)
+
     def fragment(self, batch, chain, mtu=1500, select=None, which_ip=0, only_split=False, plan_only=False,
                  out_cap=None, dst_bytes=None, hits=None, host=False, stream=None):
         """pkt_frag_batch: every packet whose L3 length is above its mtu becomes IPv4 fragments, every other packet
@@ -2028,6 +2035,193 @@ class Nat:
     def close(self):
         if getattr(self, "_t", None):
             self._L.pkt_nat_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+METER_GREEN, METER_YELLOW, METER_RED, METER_UNMETERED = range(4)
+METER_SRTCM, METER_TRTCM, METER_PASS, METER_DROP, METER_REMARK = (schema.METER_SRTCM, schema.METER_TRTCM, schema.METER_PASS,
+                                                                  schema.METER_DROP, schema.METER_REMARK)
+_METER_OUT = (("color", np.uint8), ("passed", np.uint8), ("marked", np.uint8))
+
+
+def ns_from_sec_usec(ts_sec, ts_usec):
+    """A capture's timestamps (the ts_sec and ts_usec columns of a pcap index) as the uint64 nanoseconds Meters.run's
+    `time` takes: numpy arrays or torch tensors, elementwise."""
+    if isinstance(ts_sec, np.ndarray) or np.isscalar(ts_sec):
+        return np.asarray(ts_sec).astype(np.uint64) * np.uint64(10 ** 9) + np.asarray(ts_usec).astype(np.uint64) * np.uint64(1000)
+    torch = _torch()
+    ns = ts_sec.to(torch.int64) * 10 ** 9 + ts_usec.to(torch.int64) * 1000  # below 2^63 for every 32-bit second
+    return ns.view(torch.uint64)
+
+
+def meter_cfgs(cfgs):
+    """Meter configurations as a C-contiguous array of schema.METER_CFG_DTYPE (pkt_meter_cfg_t): such an array passes
+    through; otherwise an iterable of dicts with cir, cbs and optionally pir, xbs (EBS for srTCM, PBS for trTCM), mode
+    ("srtcm" / "trtcm" or the number), color_aware, action (three of "pass" / "drop" / "remark" or the numbers, for
+    green, yellow, red; default pass, pass, drop) and dscp (three of 0..63)."""
+    if isinstance(cfgs, np.ndarray):
+        if cfgs.dtype != schema.METER_CFG_DTYPE:
+            raise ValueError("meters: a cfg array must have schema.METER_CFG_DTYPE")
+        return np.ascontiguousarray(cfgs).reshape(-1)
+    cfgs = list(cfgs)
+    arr = np.zeros(len(cfgs), schema.METER_CFG_DTYPE)
+    for i, d in enumerate(cfgs):
+        bad = set(d) - {"cir", "pir", "cbs", "xbs", "mode", "color_aware", "action", "dscp"}
+        if bad:
+            raise ValueError(f"meters: unknown cfg keys {sorted(bad)}")
+        arr["cir"][i], arr["pir"][i] = int(d["cir"]), int(d.get("pir", 0))
+        arr["cbs"][i], arr["xbs"][i] = int(d["cbs"]), int(d.get("xbs", 0))
+        mode = d.get("mode", schema.METER_SRTCM)
+        arr["mode"][i] = schema.METER_MODE[mode] if isinstance(mode, str) else int(mode)
+        arr["flags"][i] = schema.METER_F_COLOR_AWARE if d.get("color_aware") else 0
+        act = d.get("action", ("pass", "pass", "drop"))
+        arr["action"][i] = [schema.METER_ACTION[a] if isinstance(a, str) else int(a) for a in act]
+        arr["dscp"][i] = [int(x) for x in d.get("dscp", (0, 0, 0))]
+    return arr
+
+
+class MeterResult:
+    """What Meters.run gives: color (uint8 [n]: pktgpu.METER_GREEN / _YELLOW / _RED / _UNMETERED), passed (uint8 [n]: 0
+    for a packet its colour's action drops; pcap_write's `select`), marked (uint8 [n]: 1 where a DSCP was written);
+    hits / bytes (uint64 [4], per colour) where they were asked for.  Outputs not asked for are None."""
+
+    def __init__(self, **kw):
+        self.color = self.passed = self.marked = self.hits = self.bytes = None
+        self.__dict__.update(kw)
+
+
+class Meters:
+    """pkt_meter_t: a table of srTCM (RFC 2697) / trTCM (RFC 2698) policers and the metering of a batch (Parser.meters).
+    Meters(parser, ...) lives on the parser's device and takes and gives device tensors; Meters(None, ...) is the host
+    handle over numpy arrays (the sequential model, no device).
+
+        m = p.meters([dict(cir=125_000_000, cbs=1 << 16, xbs=1 << 17)] * nflows, adjust=20)
+        u = table.update(keys)                                   # its flow_id is the meter index
+        r = m.run(st.batch(), meter=u["flow_id"], time=pktgpu.ns_from_sec_usec(ts_sec, ts_usec))
+        p.pcap_write(..., select=r.passed)
+    """
+
+    def __init__(self, parser, cfgs, adjust=0):
+        from . import _lib
+        self._lib = _lib
+        self._L = _lib.load()
+        self.parser = parser
+        self.cfgs = meter_cfgs(cfgs)
+        self.nmeters = int(self.cfgs.size)
+        self.adjust = int(adjust)
+        if not -(1 << 31) <= self.adjust < (1 << 31):
+            raise ValueError("meters: adjust is an int32")
+        args = (self.cfgs.ctypes.data if self.nmeters else None, self.nmeters, self.adjust)
+        h = ctypes.c_void_p()
+        self._t = None
+        if parser is None:
+            rc = self._L.pkt_meter_create_host(*args, ctypes.byref(h))
+            if rc != 0:
+                msg = self._L.pkt_meter_last_error(None)
+                raise ValueError(f"pkt_meter_create_host failed ({rc}): {msg.decode() if msg else ''}")
+        else:
+            parser._check(self._L.pkt_meter_create(parser._ctx, *args, ctypes.byref(h)), "pkt_meter_create")
+        self._t = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self._L.pkt_meter_last_error(self._t)
+            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+    def run(self, batch, chain=None, meter=0, now=0, time=None, in_color=None, select=None, mark=False, which_ip=0,
+            outputs=("color", "passed", "marked"), counters=None, stream=None):
+        """pkt_meter_batch: meter the batch -> MeterResult.  `meter`: one index for every packet, or a uint32 [n]
+        array (a flow_id, a rule id, a port; an index at or above nmeters leaves the packet unmetered).  `now`: the
+        batch's time in ns, or `time`: a uint64 [n] array of per-packet times (ns_from_sec_usec).  `in_color` (uint8
+        [n]): the colour a colour-aware meter starts from.  `select` (uint8 [n]): a packet whose byte is 0 is
+        unmetered.  mark=True writes the DSCP of the REMARK actions IN PLACE and needs `chain` (`which_ip` as
+        Lpm.lookup takes it).  `outputs`: which of "color", "passed", "marked" to produce.  counters: True allocates
+        zeroed uint64 [4] hits and bytes and returns them; a (hits, bytes) pair passed in is accumulated into (either
+        may be None).  `batch` / `chain`: the forms Lpm.lookup takes.  Device tensors for a device handle, numpy arrays
+        for a host handle.  Asynchronous on `stream`."""
+        bad = set(outputs) - {k for k, _ in _METER_OUT}
+        if bad:
+            raise ValueError(f"meters: unknown outputs {sorted(bad)}")
+        if mark and chain is None:
+            raise ValueError("meters: mark=True needs the chain")
+        if isinstance(batch, (tuple, list)):
+            batch = dict(zip(("slab", "offsets", "lens"), batch))
+        g = lambda k: batch.get(k)  # noqa: E731
+        host = self.parser is None
+        nc = schema.METER_COLORS
+        meter_all, meter_arr = (int(meter), None) if isinstance(meter, (int, np.integer)) else (0, meter)
+        if host:
+            slab = batch["slab"]
+            if mark and not (isinstance(slab, np.ndarray) and slab.dtype == np.uint8 and slab.flags.c_contiguous
+                             and slab.flags.writeable):
+                raise ValueError("meters: the host handle remarks batch['slab'] in place: a writeable C-contiguous uint8 array")
+            b, keep = _host_batch(self._lib, batch)
+            ch = None
+            if chain is not None:
+                cols = (np.ascontiguousarray(chain["n_hdrs"], np.uint8), np.ascontiguousarray(chain["hdr_type"], np.uint8),
+                        np.ascontiguousarray(chain["hdr_off"], np.uint16))
+                ch = self._lib.PktChain(*[c.ctypes.data for c in cols])
+            meter_arr = None if meter_arr is None else np.ascontiguousarray(meter_arr, np.uint32)
+            time = None if time is None else np.ascontiguousarray(time, np.uint64)
+            in_color = None if in_color is None else np.ascontiguousarray(in_color, np.uint8)
+            select = None if select is None else np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)
+            for a in (meter_arr, time, in_color, select):
+                assert a is None or a.size >= b.n, "meters: a per-packet array is shorter than the batch"
+            res = {k: np.zeros(b.n, dt) for k, dt in _METER_OUT if k in outputs}
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+            zeros = lambda: np.zeros(nc, np.uint64)  # noqa: E731
+            ok = lambda c: isinstance(c, np.ndarray) and c.dtype == np.uint64 and c.size == nc and c.flags.c_contiguous  # noqa: E731
+        else:
+            torch = _torch()
+            b = self.parser._batch(batch["slab"], g("n"), g("stride"), g("offsets"), g("lens"))
+            ch = None if chain is None else self.parser._chain(chain)
+            for a, dt in ((meter_arr, torch.uint32), (time, torch.uint64), (in_color, torch.uint8), (select, torch.uint8)):
+                assert a is None or (a.is_cuda and a.dtype == dt and a.is_contiguous() and a.numel() >= b.n)
+            dev = self.parser.torch_device
+            res = {k: torch.empty(b.n, dtype=_tdtype(dt), device=dev) for k, dt in _METER_OUT if k in outputs}
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+            zeros = lambda: torch.zeros(nc, dtype=torch.uint64, device=dev)  # noqa: E731
+            ok = lambda c: c.is_cuda and c.dtype == torch.uint64 and c.numel() == nc and c.is_contiguous()  # noqa: E731
+        hits, nbytes = (zeros(), zeros()) if counters is True else (None, None) if not counters else counters
+        for name, c in (("hits", hits), ("bytes", nbytes)):
+            if c is not None:
+                assert ok(c), f"meters: {name} is a contiguous uint64 [{nc}] array"
+                res[name] = c
+        self._check(self._L.pkt_meter_batch(self._t, ctypes.byref(b), None if ch is None else ctypes.byref(ch),
+                                            int(which_ip), schema.METER_MARK if mark else 0, meter_all & 0xFFFFFFFF,
+                                            ptr(meter_arr), int(now) & 0xFFFFFFFFFFFFFFFF, ptr(time), ptr(in_color),
+                                            ptr(select), *[ptr(res.get(k)) for k, _ in _METER_OUT], ptr(hits), ptr(nbytes),
+                                            None if host else self.parser._stream(stream)), "pkt_meter_batch")
+        return MeterResult(**res)
+
+    def export(self, first=0, count=None):
+        """pkt_meter_export (blocking) -> a numpy array of schema.METER_STATE_DTYPE: the buckets (10^-9 byte), `last`
+        (ns) and the per-colour packet and byte counters of meters [first, first + count)."""
+        count = self.nmeters - first if count is None else int(count)
+        if self.parser is None:
+            st = np.zeros(count, schema.METER_STATE_DTYPE)
+            self._check(self._L.pkt_meter_export(self._t, first, count, st.ctypes.data if count else None), "pkt_meter_export")
+            return st
+        torch = _torch()
+        size = schema.METER_STATE_DTYPE.itemsize
+        t = torch.zeros(max(count, 1) * size, dtype=torch.uint8, device=self.parser.torch_device)
+        self._check(self._L.pkt_meter_export(self._t, first, count, t.data_ptr()), "pkt_meter_export")
+        return t.cpu().numpy()[:count * size].view(schema.METER_STATE_DTYPE).copy()
+
+    def reset(self, stream=None):
+        """pkt_meter_reset: full buckets, last = 0, zero counters, as after create.  Asynchronous on `stream`."""
+        self._check(self._L.pkt_meter_reset(self._t, None if self.parser is None else self.parser._stream(stream)),
+                    "pkt_meter_reset")
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self._L.pkt_meter_destroy(self._t)
             self._t = None
 
     def __del__(self):

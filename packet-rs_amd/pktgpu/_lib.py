@@ -114,6 +114,17 @@ class PktNatRecord(ctypes.Structure):
                 ("zero", ctypes.c_uint16), ("last_seen", ctypes.c_uint32)]
 
 
+class PktMeterCfg(ctypes.Structure):
+    _fields_ = [("cir", ctypes.c_uint64), ("pir", ctypes.c_uint64), ("cbs", ctypes.c_uint32), ("xbs", ctypes.c_uint32),
+                ("mode", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("action", ctypes.c_uint8 * 3),
+                ("dscp", ctypes.c_uint8 * 3)]
+
+
+class PktMeterState(ctypes.Structure):
+    _fields_ = [("c", ctypes.c_uint64), ("x", ctypes.c_uint64), ("last", ctypes.c_uint64),
+                ("packets", ctypes.c_uint64 * 3), ("bytes", ctypes.c_uint64 * 3)]
+
+
 class PktTunnelEntry(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint8), ("ipver", ctypes.c_uint8), ("ttl", ctypes.c_uint8), ("tos", ctypes.c_uint8),
                 ("flags", ctypes.c_uint32), ("id", ctypes.c_uint32), ("sport_lo", ctypes.c_uint16),
@@ -344,6 +355,17 @@ SIGNATURES = {
     "pkt_nat_clear": (ctypes.c_int, [_P, _P]),
     "pkt_nat_destroy": (ctypes.c_int, [_P]),
     "pkt_nat_last_error": (ctypes.c_char_p, [_P]),
+    "pkt_sizeof_meter_cfg": (ctypes.c_size_t, []),
+    "pkt_sizeof_meter_state": (ctypes.c_size_t, []),
+    "pkt_meter_create": (ctypes.c_int, [_P, _P, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_P)]),
+    "pkt_meter_create_host": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_P)]),
+    "pkt_meter_batch": (ctypes.c_int, [_P, ctypes.POINTER(PktBatch), ctypes.POINTER(PktChain), ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P,
+                                       _P, _P]),
+    "pkt_meter_reset": (ctypes.c_int, [_P, _P]),
+    "pkt_meter_export": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, _P]),
+    "pkt_meter_destroy": (ctypes.c_int, [_P]),
+    "pkt_meter_last_error": (ctypes.c_char_p, [_P]),
     "pkt_sizeof_tunnel_entry": (ctypes.c_size_t, []),
     "pkt_tunnel_create": (ctypes.c_int, [_P, _P, ctypes.c_uint32, ctypes.POINTER(_P)]),
     "pkt_tunnel_create_host": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(_P)]),
@@ -459,6 +481,8 @@ def load():
             or L.pkt_sizeof_fwd_adj() != ctypes.sizeof(PktFwdAdj) \
             or L.pkt_sizeof_nat_static() != ctypes.sizeof(PktNatStatic) \
             or L.pkt_sizeof_nat_record() != ctypes.sizeof(PktNatRecord) \
+            or L.pkt_sizeof_meter_cfg() != ctypes.sizeof(PktMeterCfg) \
+            or L.pkt_sizeof_meter_state() != ctypes.sizeof(PktMeterState) \
             or L.pkt_sizeof_tunnel_entry() != ctypes.sizeof(PktTunnelEntry):
         raise ImportError("libpktgpu struct layout mismatch with pktgpu/_lib.py")
     _lib = L

@@ -73,6 +73,19 @@ NAT_REC_STATIC = 1
 NAT_MAX_ADDR, NAT_MAX_STATIC = 64, 4096
 NAT_PROTOS = (6, 17, 1)  # protocol index p -> IP protocol
 
+# pkt_meter_* (srTCM / trTCM policers): colours, modes, the cfg flag, actions, the call flag, limits
+METER_GREEN, METER_YELLOW, METER_RED, METER_UNMETERED = range(4)
+METER_COLOR = ["GREEN", "YELLOW", "RED", "UNMETERED"]
+METER_COLORS = 4
+METER_SRTCM, METER_TRTCM = 0, 1
+METER_MODE = {"srtcm": METER_SRTCM, "trtcm": METER_TRTCM}
+METER_F_COLOR_AWARE = 1
+METER_PASS, METER_DROP, METER_REMARK = range(3)
+METER_ACTION = {"pass": METER_PASS, "drop": METER_DROP, "remark": METER_REMARK}
+METER_MARK = 1           # call flags: do the REMARK stores
+METER_MAX_METERS, METER_MAX_RATE, METER_MAX_BURST = 1 << 24, 1 << 40, 1 << 26
+METER_UNIT = 10 ** 9     # bucket units per byte
+
 # pkt_frag_* (IPv4 fragmentation to a per-packet MTU)
 (FRAG_FITS, FRAG_SPLIT, FRAG_SKIPPED, FRAG_NO_IP, FRAG_SPAN, FRAG_IPV6, FRAG_BAD_HDR, FRAG_TRUNC, FRAG_DF,
  FRAG_MTU) = range(10)
@@ -176,6 +189,12 @@ NAT_STATIC_DTYPE = np.dtype([("in_addr", np.uint8, 4), ("out_addr", np.uint8, 4)
 NAT_RECORD_DTYPE = np.dtype([("in_addr", np.uint8, 4), ("out_addr", np.uint8, 4), ("in_port", np.uint16),
                              ("out_port", np.uint16), ("proto", np.uint8), ("flags", np.uint8), ("zero", np.uint16),
                              ("last_seen", np.uint32)])
+
+# pkt_meter_cfg_t and pkt_meter_state_t as numpy records
+METER_CFG_DTYPE = np.dtype([("cir", np.uint64), ("pir", np.uint64), ("cbs", np.uint32), ("xbs", np.uint32),
+                            ("mode", np.uint8), ("flags", np.uint8), ("action", np.uint8, 3), ("dscp", np.uint8, 3)])
+METER_STATE_DTYPE = np.dtype([("c", np.uint64), ("x", np.uint64), ("last", np.uint64), ("packets", np.uint64, 3),
+                              ("bytes", np.uint64, 3)])
 
 # pkt_hdr_type_t -> Header::name() of the reference (headers.rs:529-827)
 HDR_NAMES = [

@@ -25,14 +25,16 @@ C_SCALARS = {"uint8_t": "u8", "uint16_t": "u16", "uint32_t": "u32", "uint64_t": 
              "pkt_lpm_t": "PktLpm", "pkt_fwd_adj_t": "PktFwdAdj", "pkt_fwd_t": "PktFwd",
              "pkt_scan_pattern_t": "PktScanPattern", "pkt_scan_info_t": "PktScanInfo", "pkt_scan_t": "PktScan",
              "pkt_icmp_cfg_t": "PktIcmpCfg", "pkt_nat_static_t": "PktNatStatic", "pkt_nat_record_t": "PktNatRecord",
-             "pkt_nat_t": "PktNat", "pkt_tunnel_entry_t": "PktTunnelEntry", "pkt_tunnel_t": "PktTunnel"}
+             "pkt_nat_t": "PktNat", "pkt_tunnel_entry_t": "PktTunnelEntry", "pkt_tunnel_t": "PktTunnel",
+             "pkt_meter_cfg_t": "PktMeterCfg", "pkt_meter_state_t": "PktMeterState", "pkt_meter_t": "PktMeter"}
 STRUCTS = {"pkt_batch": "PktBatch", "pkt_out": "PktOut", "pkt_field_spec": "PktFieldSpec", "pkt_chain": "PktChain",
            "pkt_gen_field": "PktGenField", "pkt_gather_piece": "PktGatherPiece", "pkt_cmp_summary": "PktCmpSummary",
            "pkt_edit_op": "PktEditOp", "pkt_flow_key": "PktFlowKey", "pkt_flow_record": "PktFlowRecord",
            "pkt_match_term": "PktMatchTerm", "pkt_match_rule": "PktMatchRule", "pkt_lpm_route": "PktLpmRoute",
            "pkt_lpm_info": "PktLpmInfo", "pkt_fwd_adj": "PktFwdAdj", "pkt_scan_pattern": "PktScanPattern",
            "pkt_scan_info": "PktScanInfo", "pkt_icmp_cfg": "PktIcmpCfg", "pkt_nat_static": "PktNatStatic",
-           "pkt_nat_record": "PktNatRecord", "pkt_tunnel_entry": "PktTunnelEntry"}
+           "pkt_nat_record": "PktNatRecord", "pkt_tunnel_entry": "PktTunnelEntry", "pkt_meter_cfg": "PktMeterCfg",
+           "pkt_meter_state": "PktMeterState"}
 
 
 def _strip(src):
@@ -122,7 +124,7 @@ def generate():
         for f, t in fields:
             lines.append(f"    pub {f}: {t},")
         lines.append("}")
-    for opaque in ("PktCtx", "PktGen", "PktMgpu", "PktPcapStream", "PktFlowTable", "PktMatch", "PktDispatch", "PktLpm", "PktFwd", "PktScan", "PktNat", "PktTunnel"):
+    for opaque in ("PktCtx", "PktGen", "PktMgpu", "PktPcapStream", "PktFlowTable", "PktMatch", "PktDispatch", "PktLpm", "PktFwd", "PktScan", "PktNat", "PktTunnel", "PktMeter"):
         lines.append(f"#[repr(C)] pub struct {opaque} {{ _p: [u8; 0] }}")
     lines += ["", '#[link(name = "pktgpu")]', 'extern "C" {']
     for name, (args, ret) in fn.items():
